@@ -22,6 +22,11 @@ oracle's; tests/test_gpu_parity.py).
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via torch.distributed.run (one rank
 per GPU, RCCL). Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line of their figures (metric, value, ms_per_step,
+config). --full adds what takes runs of its own: the roofline (a counting launch), the single-frame latencies, the
+CPU baselines (the reference itself on this host) and the N > 1 render-only pass. --dump-outputs DIR writes the
+last timed step's frame as .npy (the same camera path and scene in every run, so two builds compare pixel by pixel).
 """
 import argparse
 import json
@@ -186,6 +191,50 @@ def cpu_baseline(scene_files, W, H, gpu_rays_for_rows, args, threads):
     return out
 
 
+def pick_scene_cache():
+    """Where prt.scenes extracts and generates the scenes (PRT_SCENE_CACHE, read when prt.scenes is imported): the
+    tree's .scene_cache as ever when this user can write there; in a checkout this user may only read, a directory
+    of the user's own (the cache directory under the home, else the temporary directory), so that a run never needs
+    to write into the tree. An explicit PRT_SCENE_CACHE stays."""
+    if os.environ.get("PRT_SCENE_CACHE"):
+        return
+    import tempfile
+    own = os.path.join("parallel-ray-tracer_amd", "scene_cache")
+    for d in (os.path.join(ROOT, ".scene_cache"),
+              os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), own),
+              os.path.join(tempfile.gettempdir(), f"{own.replace(os.sep, '_')}_{os.getuid()}")):
+        try:
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, ".lock"), "a"):  # (prt.scenes' own lock file: the directory takes new files)
+                pass
+        except OSError:
+            continue
+        if d != os.path.join(ROOT, ".scene_cache"):
+            os.environ["PRT_SCENE_CACHE"] = d
+        return
+    sys.exit("bench.py: no writable directory for the scene cache (set PRT_SCENE_CACHE)")
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: the most the files hold together
+
+
+def dump_outputs(path, px, bgra):
+    """--dump-outputs: one frame as the timed launches left it (px: [H, W, 1] packed BGRA8 pixels or [H, W, 3] f32
+    rgb, on the device) -> path/bgra.npy [H, W, 4] or path/rgb.npy [H, W, 3], float32. A frame above DUMP_BYTES is
+    sampled: the same seeded pixels in every run, [n, C], their flat indices in path/pixel_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(px.cpu().numpy())
+    H, W = a.shape[:2]
+    a = (a.view(np.uint8).reshape(H, W, 4) if bgra else a.reshape(H, W, 3)).astype(np.float32)
+    if a.nbytes > DUMP_BYTES:
+        cap = DUMP_BYTES // (4 * a.shape[2] + 8)  # (a pixel's floats + its index)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=cap, replace=False))
+        np.save(os.path.join(path, "pixel_index.npy"), idx.astype(np.float64))
+        a = a.reshape(H * W, -1)[idx]
+    np.save(os.path.join(path, "bgra.npy" if bgra else "rgb.npy"), a)
+
+
 def spawn_ranks(n):
     """torch.distributed.run with n ranks on this node (rendezvous on 127.0.0.1, a free port) as a child
     process running this same command line; returns its exit status (non-zero if any rank failed)"""
@@ -203,6 +252,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64, help="timed frames")
     ap.add_argument("--warmup", type=int, default=16, help="untimed frames (after the tuning launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need, each with runs of "
+                         "its own: the roofline's counting launch, the single-frame latencies, the CPU baselines and, "
+                         "at N > 1, the render-only pass behind config.ranks (default: the line holds the timed steps' "
+                         "figures and the configuration only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes the last timed step's frame (gathered) as DIR/<name>.npy, "
+                         "float32: bgra [H, W, 4] (the quantised pixel's bytes B, G, R, A) with --output bgra8, rgb "
+                         "[H, W, 3] with --output rgb; a frame above 60 MiB is sampled (a fixed, seeded set of pixels, "
+                         "their flat indices y * W + x in DIR/pixel_index.npy, float64)")
     ap.add_argument("--frames", type=int, default=0,
                     help="frames per launch, at most --steps (0: 32 at N = 1, 16 at N > 1, where two streams' "
                          "alternating launches and the ping-pong gathers want at least two launches)")
@@ -256,6 +315,7 @@ def main():
                          "which agree on a gather's failure) and, x 2.5, on the whole run (a watchdog prints every thread's stack and "
                          "exits non-zero): a first multi-GPU run that deadlocks fails loudly instead of hanging")
     args = ap.parse_args()
+    pick_scene_cache()  # (before the ranks are started: they inherit the choice)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes (one per GPU, before
@@ -515,7 +575,7 @@ def main():
     # kernel ms per frame, and the exposed gather -- the timed region's wall time minus the slowest rank's wall time
     # for the same launches rendered without their gathers (each rank timed alone: no barrier inside)
     ranks_detail = None
-    if world > 1:
+    if world > 1 and args.full:
         kmed = sorted(kfull)[len(kfull) // 2] / F
         launch_no[0] = 0  # (the same contexts in the same order as the timed launches)
         torch.cuda.synchronize()
@@ -545,6 +605,9 @@ def main():
         data = host.bmp_from_bgra(px) if bgra else host.bmp_encode(px)
         with open(args.bmp, "wb") as fbmp:
             fbmp.write(data)
+    if args.dump_outputs and rank == 0:  # the last timed step: the last frame of the last timed launch (untimed)
+        frames = ng.frames_of(latest[2]) if gmode == "native" else (fg.frame if world > 1 else fg.target(latest[0]))
+        dump_outputs(args.dump_outputs, frames if frames.dim() == 3 else frames[latest[1] - 1], bgra)
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     rays_t = torch.tensor([rays_local], dtype=torch.float64, device="cuda")
     if dist:
@@ -562,6 +625,53 @@ def main():
                                 "without their gathers (timed alone after the timed region); exposed_gather_ms = the "
                                 "timed region's wall time (max over ranks) - the slowest rank's render_wall_ms")
 
+    def shutdown():
+        if ng:
+            ng.close()
+        for rr_ in rends:
+            rr_.close()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    # the line of a plain run: the timed steps' figures and what they ran (nothing below is needed for them)
+    result = {
+        "metric": METRIC,
+        "value": rays_total / elapsed / 1e6,
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "full": args.full,
+        "data": data_note(args.scene, scene.n_triangles, is_standin),
+        "config": {"workload": f"{args.scene} {W}x{H}, {args.spp} spp, {args.bounces} bounces, one fused "
+                               f"traversal+intersect+shade persistent launch per batch of {F} frames, "
+                               f"output {args.output}",
+                   "scene": args.scene, "triangles": scene.n_triangles, "lights": len(scene.lights),
+                   "width": W, "height": H, "bvh": args.bvh, "accel": args.accel, "kernel": args.kernel,
+                   "rays_per_frame": rays_frame, "output": args.output, "parallelism": f"{B}-row blocks cyclic x{world} + RCCL gather"
+                   if world > 1 else "single GPU", "frames_per_launch": F, "gather": gather_note,
+                   # the native gather's communicator over the whole run: gathers, row-set exchanges (1 per layout)
+                   "gather_comm": ng.info() if ng else None,
+                   # ranks: the N > 1 diagnostics, which take a render-only pass of their own (--full)
+                   "gather_mode": gmode, "ranks": ranks_detail,
+                   "launch": timed_launch, "accel_built": info["accel_built"], "accel_build_ms": info["build_ms"],
+                   # its stages over every view: GPU PLOC, host treelet passes, host layout + 8-wide collapse
+                   "accel_build_stages_ms": {k: info[k] for k in ("ploc_ms", "treelet_ms", "collapse_ms")},
+                   "wide_depth": info["wide_depth"]},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        shutdown()
+        return
+
+    # --full: everything from here on measures with runs of its own and adds its fields to the line
     # algorithmic bytes of this rank's full-batch launch: one extra untimed launch with traversal counters
     # (the timed launches' own configuration; a hybrid single frame's counters are its whole-frame kernel's, or
     # k_persist's when hot tiles went to k_coop: the counting launch never measures or tries)
@@ -689,32 +799,7 @@ def main():
             roof = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": hbm_gbs / HBM_PEAK_GBS}
         result = {
-            "metric": METRIC,
-            "value": rays_total / elapsed / 1e6,
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / K * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": data_note(args.scene, scene.n_triangles, is_standin),
-            "config": {"workload": f"{args.scene} {W}x{H}, {args.spp} spp, {args.bounces} bounces, one fused "
-                                   f"traversal+intersect+shade persistent launch per batch of {F} frames, "
-                                   f"output {args.output}",
-                       "scene": args.scene, "triangles": scene.n_triangles, "lights": len(scene.lights),
-                       "width": W, "height": H, "bvh": args.bvh, "accel": args.accel, "kernel": args.kernel,
-                       "rays_per_frame": rays_frame, "output": args.output, "parallelism": f"{B}-row blocks cyclic x{world} + RCCL gather"
-                       if world > 1 else "single GPU", "frames_per_launch": F, "gather": gather_note,
-                       # the native gather's communicator over the whole run: gathers, row-set exchanges (1 per layout)
-                       "gather_comm": ng.info() if ng else None,
-                       "gather_mode": gmode, "ranks": ranks_detail,
-                       "launch": timed_launch, "accel_built": info["accel_built"], "accel_build_ms": info["build_ms"],
-                       # its stages over every view: GPU PLOC, host treelet passes, host layout + 8-wide collapse
-                       "accel_build_stages_ms": {k: info[k] for k in ("ploc_ms", "treelet_ms", "collapse_ms")},
-                       "wide_depth": info["wide_depth"]},
+            **result,
             "frame_latency_ms": lat.item() if not args.no_latency else None,
             "frame_latency_detail": {"default_rule_ms": lat_default, "default_rule_mean_ms": sd["mean"],
                                      "refresh_frame_ms": sd["refresh_ms"], "walkthrough_ms": lat_walk,
@@ -829,13 +914,7 @@ def main():
             except Exception as e:  # reported, never silently replaced
                 result["cpu_baseline"] = {"error": repr(e)}
         print(json.dumps(result), flush=True)
-    if ng:
-        ng.close()
-    for rr_ in rends:
-        rr_.close()
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    shutdown()
 
 
 if __name__ == "__main__":

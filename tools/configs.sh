@@ -1,11 +1,12 @@
 #!/bin/bash
-# BASELINE.json's configurations on one GPU: one bench line each (the driver's 20 steps: one 20-frame launch; no CPU baseline),
-# with the autotuner's decision logged (PRT_TUNE_LOG). Output: gpurun_out/cfg_<name>.log
+# BASELINE.json's configurations on one GPU: one --full bench line each (20 steps: one 20-frame launch; no CPU baseline),
+# with the autotuner's decision logged (PRT_TUNE_LOG). Output: $PRT_LOG_DIR/cfg_<name>.log (default: logs/)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+out=${PRT_LOG_DIR:-logs}
+mkdir -p "$out"
 run() {  # name args...
     local n=$1; shift
-    PRT_TUNE_LOG=1 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" > gpurun_out/cfg_$n.log 2>&1
+    PRT_TUNE_LOG=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" > "$out/cfg_$n.log" 2>&1
     local rc=$?
     echo "$n rc=$rc"
     [ $rc -eq 0 ] || exit $rc

@@ -26,15 +26,15 @@ for s in "${@:-smoke pytest bench}"; do
       smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
       pytest) run pytest_gpu 1200 python -u -m pytest tests -m gpu -x -v --durations=15 --timeout 300 --timeout-method thread ;;
       pytestall) run pytest_gpu 1200 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread ;;
-      bench)  run bench 600 python bench.py --steps 20 --warmup 5 ;;
-      benchq) run bench 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
+      bench)  run bench 600 python bench.py --full --steps 20 --warmup 5 ;;
+      benchq) run bench 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ;;
       prof)   run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
       ab)     run ab 600 python tools/ab_variants.py persist persist4 shpool shdefer coop4 ;;
       abcar)  run abcar 600 python tools/ab_variants.py --scene car_boxed persist persist4 shpool shdefer coop4 ;;
       ranks)  run ranks 300 python tools/rank_rows.py
               run ranks_car 300 python tools/rank_rows.py --scene car_boxed ;;
       final)  run pytest_gpu 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread
-              run bench 600 python bench.py --steps 20 --warmup 5
+              run bench 600 python bench.py --full --steps 20 --warmup 5
               bash tools/profile.sh ${TAG:-r5}_dragon && python3 tools/trim_prof.py gpurun_out/prof_${TAG:-r5}_dragon || exit $?
               timeout -k 10 900 bash tools/configs.sh || exit $? ;;
       *) echo "unknown step $step"; exit 2 ;;
