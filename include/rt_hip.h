@@ -277,6 +277,53 @@ enum {
                                   tile lists built on the device (no measuring frames, no host round trip) */
 };
 int rt_get_launch_info(rt_ctx* ctx, rt_launch_info* info);
+
+/* Ray queries: the reference's two traversals for the caller's own rays (device arrays), on the uploaded scene.
+ *   RT_QUERY_CLOSEST   (hit, t) = what bvh_traverse(0, &o, &d, &nd, &t, &index) leaves in index and t on the scene's
+ *                      reference BVH (cpu/src/bvh.c:317-358), the first-found rule at exact ties included; hit is the
+ *                      original triangle index
+ *   RT_QUERY_OCCLUDED  occluded = !bvh_light_traverse(0, &o, &d, &t, max_dist2) (bvh.c:269-315; no back-face
+ *                      early-out: that is light_v's and needs a normal)
+ * RT_KERNEL_FAST answers with the same bits as RT_KERNEL_STRICT: a ray the fast walks' assumptions do not cover
+ * (checked per ray: the direction's length for the view, its magnitude, the origin's distance from the scene, unit
+ * length and a finite positive max_dist2 for the occlusion walk, non-finite input, an all-zero direction; DESIGN.md
+ * §3k) walks the reference tree; whatever that walk returns is the answer, and no input is an error.
+ * A query touches nothing a render call owns: rt_download, rt_download_bmp, rt_gather, rt_get_stats,
+ * rt_get_launch_info, rt_kernel_times, rt_sync's kernel_ms and the default rule's per-shape state are what they were. */
+enum { RT_QUERY_CLOSEST = 0, RT_QUERY_OCCLUDED = 1 };
+typedef struct rt_rays {
+    const float* origin;    /* device, [n][3] f32 */
+    const float* dir;       /* device, [n][3] f32, NOT normalised by the library */
+    const float* max_dist2; /* device, [n] f32; RT_QUERY_OCCLUDED only (light_dist2 of bvh_light_traverse) */
+    int n;                  /* >= 0; 0 is RT_OK and launches nothing */
+    int kind;               /* RT_QUERY_* */
+    int kernel;             /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+    int regroup;            /* RT_QUERY_OCCLUDED with RT_KERNEL_FAST (its pool kernel): idle lanes of a wave that trigger
+                               a refill, 1..63; 0 = the library's default (16); 64 = the lockstep kernel instead. Same
+                               bits either way. RT_QUERY_CLOSEST has the lockstep kernel only: 0..64
+                               accepted, no effect */
+} rt_rays;
+typedef struct rt_ray_results { /* device pointers */
+    int* hit;      /* CLOSEST: [n] original triangle index, -1 = miss (nullable) */
+    float* t;      /* CLOSEST: [n] ray parameter, exactly what rt_outputs.t holds for a primary ray (FLT_MAX on a
+                      miss) (nullable; not both) */
+    int* occluded; /* OCCLUDED: [n] 1 = blocked, 0 = clear */
+} rt_ray_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written */
+int rt_trace_rays(rt_ctx* ctx, const rt_rays* rays, const rt_ray_results* out);
+typedef struct rt_query_info {
+    long long rays, hits;                       /* hits: CLOSEST rays that hit / OCCLUDED rays blocked */
+    long long unit_rays, short_rays, full_rays; /* rays the fast walk served from the unit / primary / full view */
+    long long strict_rays;     /* RT_KERNEL_FAST: rays outside the fast walk's domain, walked on the reference tree from
+                                  the start (RT_KERNEL_STRICT: 0, it has no such domain) */
+    long long tie_rewalks;     /* fast walks re-walked for an exact tie or a failed reference-path check */
+    long long stack_overflows; /* must be 0 */
+    float kernel_ms;           /* HIP events around the query's launch */
+} rt_query_info;
+/* counters of the last query (synchronises); RT_E_KERNEL when it overflowed a traversal stack (its results are not
+ * valid), RT_E_STATE before the first query */
+int rt_get_query_info(rt_ctx* ctx, rt_query_info* info);
+
 /* load_from_gpu(): copies the last frame's compact rows to host (synchronous); nullable args. RT_E_KERNEL when the
  * render reported a traversal-stack overflow (its frame is not valid). */
 int rt_download(rt_ctx* ctx, float* h_rgb, int* h_hit);

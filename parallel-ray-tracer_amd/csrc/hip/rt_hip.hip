@@ -30,6 +30,7 @@
 #include "rt_comm_logic.hpp"
 #include "rt_treelet.hpp"
 #include "rt_feedback.hpp"
+#include "rt_query.hpp"
 #ifndef PRT_TREELET
 #define PRT_TREELET 2  // treelet-restructuring passes over the GPU-built binary tree (0: none)
 #endif
@@ -167,6 +168,13 @@ struct rt_ctx {
     };
     std::vector<BatchRule> brules;
     long long scene_gen = 0;  // bumped by every upload
+    // ray queries (rt_trace_rays, rt_query.hpp): their own counter block ([rtd::Q_NCOUNT] counters, then the chunk
+    // counter) and event pair -- nothing a render call owns is touched
+    float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
+    unsigned long long* d_query = nullptr;
+    hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
+    bool queried = false, q_launched = false;
+    std::unordered_map<const void*, int> q_resident;  // resident workgroups of each k_query instantiation (resident())
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -991,6 +999,10 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
     ctx->amb[2] = sc->amb.z;
     ctx->has_scene = true;
     ctx->scene_gen++;
+    ctx->scene_mx = 16.0f;  // (as the inflation above: max(16, max |coordinate|))
+    for (int i = 0; i < n; i++)
+        for (const rt_vec3& c : sc->triangles[i].coords)
+            ctx->scene_mx = std::max(ctx->scene_mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
     ctx->info = rt_scene_info{};
     ctx->info.n_triangles = n;
     ctx->info.n_lights = sc->n_lights;
@@ -1998,6 +2010,113 @@ extern "C" int rt_get_launch_info(rt_ctx* ctx, rt_launch_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- ray queries (rt_query.hpp)
+namespace {
+using QFn = void (*)(rtd::QArgs);
+QFn query_kernel(int kind, bool strict, bool tq, bool pool) {
+    using rtd::k_query;
+    if (pool) return tq ? k_query<1, false, true, true> : k_query<1, false, false, true>;
+    if (kind == RT_QUERY_CLOSEST) {
+        if (strict) return k_query<0, true, false>;
+        return tq ? k_query<0, false, true> : k_query<0, false, false>;
+    }
+    if (strict) return k_query<1, true, false>;
+    return tq ? k_query<1, false, true> : k_query<1, false, false>;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_trace_rays: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_trace_rays: null rays / results");
+    if (r->kind != RT_QUERY_CLOSEST && r->kind != RT_QUERY_OCCLUDED) return arg_err(ctx, "rt_trace_rays: bad kind");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_trace_rays: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_trace_rays: negative ray count");
+    if (r->regroup < 0 || r->regroup > 64) return arg_err(ctx, "rt_trace_rays: regroup must be 0..64");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_trace_rays: null origin / dir");
+    if (r->n > 0 && r->kind == RT_QUERY_OCCLUDED && (!r->max_dist2 || !out->occluded))
+        return arg_err(ctx, "rt_trace_rays: RT_QUERY_OCCLUDED needs max_dist2 and an occluded output");
+    if (r->n > 0 && r->kind == RT_QUERY_CLOSEST && !out->hit && !out->t)
+        return arg_err(ctx, "rt_trace_rays: RT_QUERY_CLOSEST needs a hit or a t output");
+    HIPC(hipSetDevice(ctx->device));
+    if (!ctx->d_query) HIPC(hipMalloc((void**)&ctx->d_query, sizeof(unsigned long long) * (rtd::Q_NCOUNT + 1)));
+    if (!ctx->q_ev0) HIPC(hipEventCreate(&ctx->q_ev0));
+    if (!ctx->q_ev1) HIPC(hipEventCreate(&ctx->q_ev1));
+    HIPC(hipMemsetAsync(ctx->d_query, 0, sizeof(unsigned long long) * (rtd::Q_NCOUNT + 1), ctx->stream));
+    ctx->queried = true;
+    ctx->q_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::QArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s.ref = dview(ctx->ref);
+    A.s.acc = ctx->acc.nodes ? dview(ctx->acc) : A.s.ref;
+    A.s.wide = rtd::DWide{ctx->wide_nodes, ctx->wide_tris, ctx->wide_orig, ctx->wide_n};
+    A.s.unit = rtd::DWide{ctx->unit_nodes, ctx->unit_tris, ctx->unit_orig, ctx->unit_n};
+    A.s.prim = rtd::DWide{ctx->prim_nodes, ctx->prim_tris, ctx->prim_orig, ctx->prim_n};  // chosen per ray
+    A.s.faces = ctx->d_faces;
+    A.s.ref_path = ctx->ref.path;
+    A.s.n_tris = ctx->n_tris;
+    for (int a = 0; a < 3; a++) A.s.n_face[a] = (int)ctx->faces[a].size();
+    A.origin = r->origin;
+    A.dir = r->dir;
+    A.max_dist2 = r->max_dist2;
+    A.hit = out->hit;
+    A.t = out->t;
+    A.occluded = out->occluded;
+    A.counters = ctx->d_query;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_query + rtd::Q_NCOUNT);
+    A.n = r->n;
+    A.o_max = 4.0f * ctx->scene_mx;
+    const bool strict = r->kernel == RT_KERNEL_STRICT;
+    // the pool form (rt_query.hpp occluded_pool): the fast occlusion query on a wide view; regroup = its refill
+    // threshold in idle lanes (0: 16), 64 = the lockstep form instead. The closest-hit query has the lockstep form only.
+    const bool pool = r->kind == RT_QUERY_OCCLUDED && !strict && ctx->wide_n > 0 && r->regroup != 64;
+    A.regroup = r->regroup > 0 ? r->regroup : 16;
+    const QFn k = query_kernel(r->kind, strict, ctx->tq_ok, pool);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->q_resident.find((const void*)k);  // (the occupancy query once per kernel, not per query)
+    if (res == ctx->q_resident.end()) res = ctx->q_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->q_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->q_ev1, ctx->stream));
+    ctx->q_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_query_info(rt_ctx* ctx, rt_query_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->queried) {
+        ctx->err = "rt_get_query_info: no query traced";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::Q_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_query, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->rays = (long long)c[rtd::Q_RAYS];
+    info->hits = (long long)c[rtd::Q_HITS];
+    info->unit_rays = (long long)c[rtd::Q_UNIT];
+    info->short_rays = (long long)c[rtd::Q_SHORT];
+    info->full_rays = (long long)c[rtd::Q_FULL];
+    info->strict_rays = (long long)c[rtd::Q_STRICT];
+    info->tie_rewalks = (long long)c[rtd::Q_TIE];
+    info->stack_overflows = (long long)c[rtd::Q_ERR];
+    if (ctx->q_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->q_ev0, ctx->q_ev1));
+    if (c[rtd::Q_ERR]) {
+        ctx->err = "rt_get_query_info: the query's traversal stack overflowed " + std::to_string(c[rtd::Q_ERR]) +
+                   " times (BVH deeper than the walks' stacks): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -2991,6 +3110,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
                     (void*)ctx->d_full_bgra})
         if (p) (void)hipFree(p);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
+    if (ctx->d_query) (void)hipFree(ctx->d_query);
+    if (ctx->q_ev0) (void)hipEventDestroy(ctx->q_ev0);
+    if (ctx->q_ev1) (void)hipEventDestroy(ctx->q_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

@@ -101,6 +101,22 @@ class CommInfo(ctypes.Structure):  # rt_comm_info
                 ("nranks", ctypes.c_int), ("rank", ctypes.c_int)]
 
 
+class Rays(ctypes.Structure):  # rt_rays
+    _fields_ = [("origin", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("max_dist2", ctypes.c_void_p),
+                ("n", ctypes.c_int), ("kind", ctypes.c_int), ("kernel", ctypes.c_int), ("regroup", ctypes.c_int)]
+
+
+class RayResults(ctypes.Structure):  # rt_ray_results
+    _fields_ = [("hit", ctypes.c_void_p), ("t", ctypes.c_void_p), ("occluded", ctypes.c_void_p)]
+
+
+class QueryInfo(ctypes.Structure):  # rt_query_info
+    _fields_ = [("rays", ctypes.c_longlong), ("hits", ctypes.c_longlong), ("unit_rays", ctypes.c_longlong),
+                ("short_rays", ctypes.c_longlong), ("full_rays", ctypes.c_longlong),
+                ("strict_rays", ctypes.c_longlong), ("tie_rewalks", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 _host = None
 _hip = None
 
@@ -183,6 +199,8 @@ def hip():
         L.rt_comm_last_error.restype = ctypes.c_char_p
         L.rt_comm_destroy.argtypes = [ctypes.c_void_p]
         L.rt_comm_destroy.restype = None
+        L.rt_trace_rays.argtypes = [ctypes.c_void_p, P(Rays), P(RayResults)]
+        L.rt_get_query_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
         L.rt_device_count.argtypes = []
         L.rt_version.restype = ctypes.c_char_p
         _hip = L

@@ -24,6 +24,7 @@ ACCEL_NAMES = {v: k for k, v in ACCEL.items()}
 FLAG_COUNTERS = 1
 FLAG_UNPACKED_STACK = 2  # the builds scenes of more than 2^24 wide nodes run (rt_hip.h RT_FLAG_UNPACKED_STACK)
 FLAG_UNPACKED_TRIS = 4   # the builds scenes of 2^26 or more triangles run (RT_FLAG_UNPACKED_TRIS)
+QUERY_CHUNK = 256  # rays a wave of the query kernel takes at once (rt_query.hpp QUERY_CHUNK)
 
 
 class RtError(RuntimeError):
@@ -339,6 +340,71 @@ class Renderer:
         d["cold_variant"] = VARIANT_NAMES.get(d["cold_variant"], d["cold_variant"])
         d["build_bits"] = sorted(k for k, v in _lib.BUILD_BITS.items() if d["build"] & v)
         return d
+
+    def _rays(self, origins, dirs):
+        """device pointers and count of a query's rays: [n, 3] float32 contiguous tensors on this device (checked
+        before any launch), or raw pointers with n = origins' (an (int pointer, n) pair)"""
+        import torch
+        if isinstance(origins, tuple):  # raw pointers: (pointer, n); dirs a raw pointer
+            po, n = origins
+            if not isinstance(po, int) or not isinstance(dirs, int) or n < 0:
+                raise RtError("rays: raw pointers are given as origins=(pointer, n), dirs=pointer")
+            return po, dirs, int(n)
+        for x, what in ((origins, "origins"), (dirs, "dirs")):
+            if not isinstance(x, torch.Tensor):
+                raise RtError(f"{what}: expected a torch tensor or a raw (pointer, n), got {type(x).__name__}")
+            if x.dim() != 2 or x.shape[1] != 3:
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, 3]")
+        n = origins.shape[0]
+        if dirs.shape[0] != n:
+            raise RtError(f"dirs: {dirs.shape[0]} rays, origins has {n}")
+        f32 = (torch.float32,)
+        return _ptr(origins, "origins", 3 * n, f32, self.device), _ptr(dirs, "dirs", 3 * n, f32, self.device), n
+
+    def _trace(self, rays, res):
+        self._chk(_L.rt_trace_rays(self._ctx, ctypes.byref(rays), ctypes.byref(res)), "rt_trace_rays")
+
+    def trace_rays(self, origins, dirs, kernel="auto", hit=None, t=None, regroup=0):
+        """rt_trace_rays(RT_QUERY_CLOSEST): the closest hit of each ray o + t d, as the reference's bvh_traverse
+        finds it (bit-exact, first-found at exact ties) -> (hit [n] int32: original triangle index, -1 = miss;
+        t [n] float32: the ray parameter, FLT_MAX on a miss). origins / dirs: [n, 3] float32 contiguous tensors on
+        this device (dirs are not normalised), or origins=(pointer, n), dirs=pointer; hit / t: optional outputs
+        (allocated when not given). Asynchronous on the renderer's stream: sync() or query_info() before the results
+        are read on another stream."""
+        import torch
+        po, pd, n = self._rays(origins, dirs)
+        dev = f"cuda:{self.device}"
+        if hit is None:
+            hit = torch.empty(n, dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+        res = _lib.RayResults(_ptr(hit, "hit", n, (torch.int32,), self.device),
+                              _ptr(t, "t", n, (torch.float32,), self.device), None)
+        self._trace(_lib.Rays(po, pd, None, n, 0, KERNELS.get(kernel, kernel), regroup), res)
+        return hit, t
+
+    def occluded(self, origins, dirs, max_dist2, kernel="auto", out=None, regroup=0):
+        """rt_trace_rays(RT_QUERY_OCCLUDED): out[i] = 1 when the reference's bvh_light_traverse finds a triangle
+        on ray i nearer than max_dist2[i] (a squared distance, [n] float32), else 0 -> out [n] int32.
+        regroup (fast kernel): the pool kernel's refill threshold in idle lanes (0: the default; 64: the lockstep
+        kernel instead); the answer does not depend on it"""
+        import torch
+        po, pd, n = self._rays(origins, dirs)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=f"cuda:{self.device}")
+        pm = _ptr(max_dist2, "max_dist2", n, (torch.float32,), self.device)
+        if pm is None:
+            raise RtError("max_dist2: expected a tensor or a raw pointer")
+        res = _lib.RayResults(None, None, _ptr(out, "out", n, (torch.int32,), self.device))
+        self._trace(_lib.Rays(po, pd, pm, n, 1, KERNELS.get(kernel, kernel), regroup), res)
+        return out
+
+    def query_info(self):
+        """rt_get_query_info: the last query's counters (rays, hits, the rays each view served, strict_rays outside
+        the fast walk's domain, tie_rewalks) and kernel_ms; synchronises; raises when the query overflowed a stack"""
+        i = _lib.QueryInfo()
+        self._chk(_L.rt_get_query_info(self._ctx, ctypes.byref(i)), "rt_get_query_info")
+        return {f: getattr(i, f) for f, _ in _lib.QueryInfo._fields_}
 
     def stats(self):
         s = Stats()

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Ray-query throughput (rt_trace_rays): per scene and ray set, `--runs` queries; one JSON line each
+with Mrays/s from the median kernel_ms (HIP events around the query's launch), the spread (min / max ms), the
+query's counters and the library's md5. Ray sets, each W x H rays:
+  primary_rows / primary_tiles / primary_perm  the reference camera's primary rays in row-major order, in 8x8-tile
+                                               order, in a fixed random permutation (CLOSEST)
+  bounce_closest                               unit-length rays from the primary hit points in random directions
+  bounce_occluded / bounce_occluded_perm       those rays as OCCLUDED with max_dist2 = 4, in pixel order and in the
+                                               permutation (about 1 % of float32-normalised directions miss the
+                                               occlusion walk's length window and walk the reference tree)
+  window_occluded / window_occluded_perm       the same with every direction inside that window (in_window)
+and, for context beside primary_rows, the frame kernel's own rate (stats()["rays"] / kernel_ms of a `persist` frame).
+The fast and the strict kernel answer with the same bits (checked here on every set).
+usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "parallel-ray-tracer_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", nargs="+", default=["dragon", "car_boxed"])
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--runs", type=int, default=7)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from prt import device, host
+    W, H = a.width, a.height
+    md5 = device.lib_md5()
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        c = torch.from_numpy(host.camera_array(host.camera(W, H))).cuda()
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device="cuda"),
+                                torch.arange(W, dtype=torch.float32, device="cuda"), indexing="ij")
+        d = ((c[1] - c[0])[None, :] + c[2][None, :] * xs.reshape(-1, 1)) + c[3][None, :] * ys.reshape(-1, 1)
+        o = c[0][None, :].expand_as(d).contiguous()
+        n = W * H
+        g = torch.Generator(device="cpu").manual_seed(1)
+        idx = torch.arange(n).reshape(H, W)
+        tiles = torch.cat([idx[y:y + 8, x:x + 8].reshape(-1) for y in range(0, H, 8) for x in range(0, W, 8)]).cuda()
+        perm = torch.randperm(n, generator=g).cuda()
+        hit, t = r.trace_rays(o, d, kernel="strict")
+        r.sync()  # (the query runs on the renderer's stream, the tensor operations below on torch's)
+        t1 = torch.where(hit >= 0, t, torch.ones_like(t))
+        bo = (o + d * t1[:, None]).contiguous()
+        bd = torch.randn(n, 3, generator=g)
+        bd = bd / bd.norm(dim=1, keepdim=True)
+        bw = in_window(bd).cuda().contiguous()
+        bd = bd.cuda().contiguous()
+        four = torch.full((n,), 4.0, device="cuda")
+        sets = [("primary_rows", o, d, None), ("primary_tiles", o[tiles].contiguous(), d[tiles].contiguous(), None),
+                ("primary_perm", o[perm].contiguous(), d[perm].contiguous(), None), ("bounce_closest", bo, bd, None),
+                ("bounce_occluded", bo, bd, four),
+                ("bounce_occluded_perm", bo[perm].contiguous(), bd[perm].contiguous(), four),
+                ("window_occluded", bo, bw, four),
+                ("window_occluded_perm", bo[perm].contiguous(), bw[perm].contiguous(), four)]
+        for label, so, sd, m in sets:
+            # the kind's forms, interleaved run by run: the occlusion query's pool (the default) and its lockstep form
+            # (regroup = 64); the closest-hit query has the lockstep form only
+            forms = [("lockstep", 64)] if m is None else [("pool", 0), ("lockstep", 64)]
+
+            def run(kernel, regroup=0):
+                if m is None:
+                    out = r.trace_rays(so, sd, kernel=kernel)
+                else:
+                    out = (r.occluded(so, sd, m, kernel=kernel, regroup=regroup),)
+                return out, r.query_info()
+            ref, _ = run("strict")
+            ms, info, same = {f: [] for f, _ in forms}, {}, {}
+            for _ in range(a.runs):
+                for f, rg in forms:
+                    out, info[f] = run("fast", rg)
+                    ms[f].append(info[f]["kernel_ms"])
+                    same[f] = all(bool((x.view(torch.int32) == y.view(torch.int32)).all()) for x, y in zip(out, ref))
+            for f, _ in forms:
+                med = statistics.median(ms[f])
+                line = {"scene": name, "set": label, "form": f, "rays": n, "mrays_s": round(n / med / 1e3, 1),
+                        "kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms[f]), 4),
+                        "kernel_ms_max": round(max(ms[f]), 4), "runs": a.runs, "equals_strict": same[f],
+                        "info": {k: v for k, v in info[f].items() if k != "kernel_ms"}, "lib_md5": md5}
+                if f != forms[-1][0]:
+                    print(json.dumps(line), flush=True)
+            if label == "primary_rows":  # context, not a bar: the frame kernel's rays per second on the same scene
+                rgb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+                fm = []
+                for _ in range(a.runs):
+                    r.render(host.camera(W, H), W, H, kernel="persist", rgb=rgb)
+                    fm.append(r.sync())
+                line["frame_persist_mrays_s"] = round(r.stats()["rays"] / statistics.median(fm) / 1e3, 1)
+            print(json.dumps(line), flush=True)
+        r.close()
+
+
+def in_window(d):
+    """directions (CPU float32 [n, 3]) whose squared length, computed as the kernel computes it ((x x + y y) + z z in
+    float32), lies in the occlusion walk's window [1 - 4u, 1 + 2u], u = 2^-24: rows outside are rescaled by
+    1 / sqrt(l2) up to three times, and what then still fails is replaced by (1, 0, 0)"""
+    import torch
+    d = d.clone()
+    lo, hi = 1.0 - 4 * 2.0 ** -24, 1.0 + 2 * 2.0 ** -24
+
+    def l2(v):
+        return (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+    for _ in range(3):
+        q = l2(d)
+        bad = (q < lo) | (q > hi)
+        d[bad] = d[bad] / torch.sqrt(q[bad])[:, None]
+    q = l2(d)
+    d[(q < lo) | (q > hi)] = torch.tensor([1.0, 0.0, 0.0])
+    return d
+
+
+if __name__ == "__main__":
+    main()
