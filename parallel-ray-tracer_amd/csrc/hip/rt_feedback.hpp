@@ -23,7 +23,7 @@ struct FbArgs {
     int pct;               // hot tiles: cost > pct % of the costliest (0: none)
     int hot_cap;           // at most this many hot-kernel tiles (the hottest; k_coop spends ~2x the wave time per ray)
     int tw, th, ctw, cth;  // the hot kernel's pixel tile (rt_coop.hpp GTile) and its tile grid
-    int xcd_mode;          // region layout of the cold tiles (rt_hip.hip region_layout): 1 rows, 2 columns, 3 blocks,
+    int xcd_mode;          // region layout of the cold tiles (rt_launch_logic.hpp region_layout): 1 rows, 2 columns, 3 blocks,
                            // 0 one region
     const unsigned char* info;  // per 8x8 tile, fixed for the shape: region (bits 0-2), its k_coop<4> tiles (bits 3-5),
                                 // its k_coop<2> tiles (bits 6-7) -- no division per tile in the kernel (fb_tile_info)

@@ -28,6 +28,7 @@
 #include "rt_output.hpp"
 #include "rt_build.hpp"
 #include "rt_comm_logic.hpp"
+#include "rt_launch_logic.hpp"
 #include "rt_treelet.hpp"
 #include "rt_feedback.hpp"
 #include "rt_query.hpp"
@@ -69,6 +70,20 @@ struct CommLink {
     rt_comm* cm = nullptr;
 };
 
+// One 8-wide quantised view (rt_wide.cpp; rt_device.hpp DWide) on the host and on the device; nodes empty / null:
+// none. tris_n: the triangles it was built over (a subset for the unit and the primary view).
+struct HostWide {
+    std::vector<float4> nodes, tris;
+    std::vector<int> orig;
+    int depth = 0, tris_n = 0;
+};
+struct DevWide {
+    float4 *nodes = nullptr, *tris = nullptr;
+    int* orig = nullptr;
+    int n = 0, depth = 0, tris_n = 0;
+    rtd::DWide view() const { return rtd::DWide{nodes, tris, orig, n}; }
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -79,18 +94,9 @@ struct rt_ctx {
     std::string err;
     // device scene
     DevView ref, acc;  // acc.nodes == nullptr: acc aliases ref
-    // 8-wide quantised view of acc (rt_wide.cpp); wide_nodes == nullptr: none
-    float4 *wide_nodes = nullptr, *wide_tris = nullptr;
-    int* wide_orig = nullptr;
-    int wide_n = 0, wide_depth = 0;
-    // the unit-direction view (rtd::DScene::unit): the wide BVH over the triangles a unit-length ray can hit
-    float4 *unit_nodes = nullptr, *unit_tris = nullptr;
-    int* unit_orig = nullptr;
-    int unit_n = 0, unit_depth = 0, unit_tris_n = 0;
-    // the primary view (rtd::DScene::prim): the wide BVH over the triangles a direction of length <= PRIMARY_D can hit
-    float4 *prim_nodes = nullptr, *prim_tris = nullptr;
-    int* prim_orig = nullptr;
-    int prim_n = 0, prim_depth = 0, prim_tris_n = 0;
+    // the 8-wide quantised views: wide, of acc's triangles; unit (rtd::DScene::unit), over the triangles a unit-length
+    // ray can hit; prim (rtd::DScene::prim), over those a direction of length <= PRIMARY_D can hit
+    DevWide wide, unit, prim;
     float4* d_shade = nullptr;
     float4* d_mats = nullptr;
     float4* d_lights = nullptr;
@@ -145,7 +151,7 @@ struct rt_ctx {
     unsigned long long* h_err = nullptr;       // pinned: the last render's error counter (rtd::C_ERR), read by rt_sync / rt_download
     std::unordered_map<long long, int*> orders;  // tile dealing orders (rt_frame.dealing), per tx x ty tile grid
     unsigned int* d_work = nullptr;
-    static constexpr int NEV = 64;  // ring of per-launch event pairs (rt_kernel_times)
+    static constexpr int NEV = rtl::NEV;  // ring of per-launch event pairs (rt_kernel_times)
     hipEvent_t ev0s[NEV] = {}, ev1s[NEV] = {};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the last launch's pair
     hipEvent_t gather_ev = nullptr;           // completion of the last rt_gather into this (root) context
@@ -153,17 +159,11 @@ struct rt_ctx {
     long long launches = 0;
     bool rendered = false;
     std::shared_ptr<CommLink> comm_link;  // the communicator with a send / recv group on this stream (CommLink)
-    // the default rule of frame batches and spp > 1 (PERSIST4 or SHPOOL), measured per shape (render_batch)
+    // the default rule of frame batches and spp > 1 (PERSIST4 or SHPOOL), measured per shape (batch_rule_pick): the
+    // trials' launch numbers (rtl::next_trial, rtl::batch_decide) and the choice
     struct BatchRule {
-        long long scene = -1;
-        int W = 0, rows = 0, off = 0, stride = 0, block = 0, shift = 0, bounces = 0, spp = 0, frames = 0, dealing = 0,
-            cap_req = 0;
-        // trials per candidate: 3, decided by the minimum -- or, for launches longer than LONG_MS, the median (the
-        // 64-spp configuration's 190-ms launches of one kernel ranged 186-199 ms on one box; the minimum of two trials
-        // picked either kernel)
-        static constexpr int ROUNDS = 3;
-        static constexpr float LONG_MS = 50.0f;
-        long long launch[2][ROUNDS] = {{-1, -1, -1}, {-1, -1, -1}};
+        rtl::ShapeKey key;
+        long long launch[2][rtl::BATCH_ROUNDS] = {{-1, -1, -1}, {-1, -1, -1}};
         int choice = -1;
     };
     std::vector<BatchRule> brules;
@@ -179,26 +179,17 @@ struct rt_ctx {
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
     struct Hybrid {
-        long long scene = -1;
-        int W = 0, rows = 0, off = 0, stride = 0, block = 0, bounces = 0, dealing = 0, pct_req = 0, hk_req = 0;
+        rtl::ShapeKey key;
         int state = 0;  // 0: measure next; 1: a measuring frame's tile times are on their way to h_tr; 2: lists ready
         long long frames = 0;  // frames since the choice or the last list refresh
-        static constexpr int NCAND = 12;
-        static constexpr int ROUNDS = 4;    // trial frames per candidate, back to back: the first untimed (its per-tile
-                                            // times feed the next one's lists), the best median of the other three
-                                            // chosen (single frames are noisy, and some two-stream launches bimodal).
-                                            // Back to back, not round robin: a hybrid candidate's lists are built from
-                                            // the frame before it, and after another candidate's frame they are not the
-                                            // lists it renders with once chosen (a car_boxed walkthrough priced its hot
-                                            // candidates 30-60 % slow and settled on none of them)
-        static constexpr int WARM = 1;
+        static constexpr int NCAND = rtl::NCAND;
+        static constexpr int ROUNDS = rtl::HYBRID_ROUNDS;  // trial frames per candidate (rtl::hybrid_decide)
         static constexpr int REFRESH = 64;  // frames of a shape between measuring frames once it is decided
-        // candidates: hot threshold (0 = the cold kernel over the whole frame), lanes per ray of k_coop for the hot
-        // tiles, the cold tiles' kernel (RT_VARIANT_PERSIST / SHPOOL); their lists at d_lists + at[c]
+        // candidates (rtl::HotCand: hot threshold, 0 = the cold kernel over the whole frame; lanes per ray of k_coop
+        // for the hot tiles; the cold tiles' kernel), their lists at d_lists + cl[c].at, their trials and times
         int nc = 0, choice = -1;
-        int pct[NCAND] = {}, lanes[NCAND] = {}, cold[NCAND] = {}, n_hot[NCAND] = {}, n_cold[NCAND] = {};
-        bool lpt[NCAND] = {};
-        size_t at[NCAND] = {};
+        rtl::HotCand cand[NCAND] = {};
+        rtl::CandLists cl[NCAND];
         long long launch[NCAND][ROUNDS] = {};
         float ms[NCAND] = {};
         unsigned long long* d_tr = nullptr;  // [tiles][4], rtd::k_persist's TRACE records
@@ -236,36 +227,12 @@ struct rt_ctx {
 
 namespace {
 
-// RT_VARIANT_HYBRID candidates: pct = 0: the cold kernel over the whole frame; else the 8x8 tiles slower than pct % of the
-// slowest tile of the measuring frame go to k_coop with `lanes` lanes per ray while the cold kernel renders the rest
-// (each candidate is tried ROUNDS times; hybrid_pick). Measured: car_boxed hot > 45 % k_coop<4>,
-// sportscar hot > 60 % k_coop<2> / <4>, dragon the whole-frame kernels; k_fan and k_relay hot tiles never won
-// (both removed).
-// lpt: the cold tiles dealt costliest first by the measuring frame's per-tile times (longest processing time first,
-// the classic makespan heuristic: a single frame ends with its slowest tile) instead of centre-out; with pct = 0 the
-// whole frame that way.
-struct HotCand {
-    int pct, lanes, cold;
-    bool lpt;
-};
-// The candidates are the configurations that won on some BASELINE scene (dragon the shadow pool in LPT
-// order, car_boxed hot > 45 % k_coop<4> with LPT cold tiles, sportscar hot > 60 % k_coop<4> / <2>) plus k_persist in
-// LPT order: few candidates keep the trial frames few (3 each) and the choice robust to frame-to-frame noise (a moving
-// camera changes every trial frame's cost; nine candidates picked a 12 % slower one on a walkthrough).
-// (RT_VARIANT_SHPOOL here stands for the rule's pool kernel: RT_VARIANT_SHDEFER where its path buffer fits.)
-constexpr HotCand HYBRID_CANDS[] = {{0, 0, RT_VARIANT_SHPOOL, true},   {0, 0, RT_VARIANT_PERSIST, true},
-                                    {45, 4, RT_VARIANT_PERSIST, true}, {60, 4, RT_VARIANT_PERSIST, false},
-                                    {60, 2, RT_VARIANT_PERSIST, false}};
 // Per-frame feedback (rt_feedback.hpp) for a decided shape: its frames deal their tiles by the previous frame's
 // per-tile durations, the lists built on the device, instead of a measuring frame's every REFRESH frames
 #ifndef PRT_FEEDBACK
 #define PRT_FEEDBACK 1
 #endif
-// pixel tile of a group kernel (rtd::GTile): k_coop<2> 8x4, k_coop<4> 4x4
-inline void hot_tile(int g, int& tw, int& th) {
-    tw = g == 2 ? 8 : 4;
-    th = 4;
-}
+using rtl::hot_tile;
 
 const char* variant_name(int v) {
     switch (v) {
@@ -301,24 +268,16 @@ void free_view(DevView& v) {
     v = DevView();
 }
 
+void free_wide(DevWide& w) {
+    for (void* p : {(void*)w.nodes, (void*)w.tris, (void*)w.orig})
+        if (p) (void)hipFree(p);
+    w = DevWide();
+}
+
 void free_scene(rt_ctx* ctx) {
     free_view(ctx->ref);
     free_view(ctx->acc);
-    for (void* p : {(void*)ctx->wide_nodes, (void*)ctx->wide_tris, (void*)ctx->wide_orig})
-        if (p) (void)hipFree(p);
-    ctx->wide_nodes = ctx->wide_tris = nullptr;
-    ctx->wide_orig = nullptr;
-    ctx->wide_n = ctx->wide_depth = 0;
-    for (void* p : {(void*)ctx->unit_nodes, (void*)ctx->unit_tris, (void*)ctx->unit_orig})
-        if (p) (void)hipFree(p);
-    ctx->unit_nodes = ctx->unit_tris = nullptr;
-    ctx->unit_orig = nullptr;
-    ctx->unit_n = ctx->unit_depth = ctx->unit_tris_n = 0;
-    for (void* p : {(void*)ctx->prim_nodes, (void*)ctx->prim_tris, (void*)ctx->prim_orig})
-        if (p) (void)hipFree(p);
-    ctx->prim_nodes = ctx->prim_tris = nullptr;
-    ctx->prim_orig = nullptr;
-    ctx->prim_n = ctx->prim_depth = ctx->prim_tris_n = 0;
+    for (DevWide* w : {&ctx->wide, &ctx->unit, &ctx->prim}) free_wide(*w);
     for (void* p : {(void*)ctx->d_shade, (void*)ctx->d_mats, (void*)ctx->d_lights, (void*)ctx->d_faces})
         if (p) (void)hipFree(p);
     ctx->d_faces = nullptr;
@@ -335,6 +294,19 @@ int upload(rt_ctx* ctx, T** dst, const std::vector<T>& src, size_t* bytes = null
     HIPC(hipMalloc((void**)dst, b));
     if (!src.empty()) HIPC(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
     if (bytes) *bytes += b;
+    return RT_OK;
+}
+
+// a wide view to the device (none: d stays empty)
+int upload_wide(rt_ctx* ctx, const HostWide& h, DevWide& d) {
+    if (h.nodes.empty()) return RT_OK;
+    int rc;
+    if ((rc = upload(ctx, &d.nodes, h.nodes)) || (rc = upload(ctx, &d.tris, h.tris)) ||
+        (rc = upload(ctx, &d.orig, h.orig)))
+        return rc;
+    d.n = (int)(h.nodes.size() / 5);
+    d.depth = h.depth;
+    d.tris_n = h.tris_n;
     return RT_OK;
 }
 
@@ -711,10 +683,42 @@ double primary_dmax(const rt_camera* c, int W, int H) {
     return m * (1.0 + 1e-5) + 1e-5 * terms;
 }
 
+// max(16, max |coordinate|) of a scene: the boxes' inflation is 2^-16 of it (rt_upload_scene), the ray queries' origin
+// bound 4x it (rt_trace_rays)
+float scene_magnitude(const rt_triangle* T, int n) {
+    float mx = 16.0f;
+    for (int i = 0; i < n; i++)
+        for (const rt_vec3& c : T[i].coords)
+            mx = std::max(mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
+    return mx;
+}
+
+// A binary tree in the reference layout collapsed to the 8-wide quantised form (rt_wide.cpp; boxes inflated, planes
+// rounded outward) over its n triangles; false: none (the collapse failed, or too deep for the wide walk's stack).
+bool collapse_wide(rt_ctx* ctx, const rt_bvh_node* nodes, int nlen, const int* idx, const rt_triangle* T, int n,
+                   float inflate, float cnode, HostWide& w) {
+    uint32_t* words = nullptr;
+    int* order = nullptr;
+    rth_wbvh_info wi{};
+    const auto t_c = std::chrono::steady_clock::now();
+    const bool built = rth_wbvh_build_cost(nodes, nlen, idx, T, n, inflate, cnode, &words, &order, &wi) == RT_OK;
+    ctx->t_collapse += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
+    const bool ok = built && wi.depth <= rtd::WSTACK;
+    if (ok) {
+        w.nodes.resize(5 * (size_t)wi.n_nodes);
+        std::memcpy(w.nodes.data(), words, sizeof(uint32_t) * 20 * (size_t)wi.n_nodes);
+        tri_records(T, order, n, w.tris, w.orig);
+        w.depth = wi.depth;
+        w.tris_n = n;
+    }
+    rth_free(words);
+    rth_free(order);
+    return ok;
+}
+
 // The 8-wide quantised view of a triangle set, built as the full view was (`method`: RT_ACCEL_GPU = PLOC on the
 // device, else the host binned SAH), same inflation and node price. RT_E_STATE: none (too deep for the wide walk).
-int wide_view(rt_ctx* ctx, const rt_triangle* T, int n, int method, int R, float inflate, float cnode,
-              std::vector<float4>& wn, std::vector<float4>& wt, std::vector<int>& wo, int& depth) {
+int wide_view(rt_ctx* ctx, const rt_triangle* T, int n, int method, int R, float inflate, float cnode, HostWide& w) {
     rt_bvh_node* nodes = nullptr;
     int nlen = 0;
     int* idx = nullptr;
@@ -734,27 +738,34 @@ int wide_view(rt_ctx* ctx, const rt_triangle* T, int n, int method, int R, float
     } else if (rth_bvh_build(T, (size_t)n, RTH_BVH_BINNED_SAH, nullptr, &nodes, &nlen, &idx, nullptr) != RT_OK) {
         return RT_E_STATE;
     }
-    uint32_t* words = nullptr;
-    int* order = nullptr;
-    rth_wbvh_info wi{};
-    int rc = RT_E_STATE;
-    const auto t_c = std::chrono::steady_clock::now();
-    const bool wide_ok = rth_wbvh_build_cost(nodes, nlen, idx, T, n, inflate, cnode, &words, &order, &wi) == RT_OK;
-    ctx->t_collapse += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
-    if (wide_ok && wi.depth <= rtd::WSTACK) {
-        wn.resize(5 * (size_t)wi.n_nodes);
-        std::memcpy(wn.data(), words, sizeof(uint32_t) * 20 * (size_t)wi.n_nodes);
-        tri_records(T, order, n, wt, wo);
-        depth = wi.depth;
-        rc = RT_OK;
-    }
-    rth_free(words);
-    rth_free(order);
+    const int rc = collapse_wide(ctx, nodes, nlen, idx, T, n, inflate, cnode, w) ? RT_OK : RT_E_STATE;
     if (!gpu) {
         rth_free(nodes);
         rth_free(idx);
     }
     return rc;
+}
+
+// The wide view over the triangles of the scene a direction of length <= dmax can hit, built as the full view was
+// (`built`, `inflate`: the full view's) -- when there are any and fewer than `fewer_than` (else the full view serves).
+// v.orig maps to the scene's triangle indices. RT_E_HIP aborts the upload; any other failure leaves v empty.
+int subset_view(rt_ctx* ctx, const rt_scene* sc, double dmax, size_t fewer_than, int built, float inflate, HostWide& v) {
+    std::vector<rt_triangle> sub;
+    std::vector<int> sub_id;
+    for (int i = 0; i < sc->n_triangles; i++)
+        if (hittable(sc->triangles[i], dmax)) {
+            sub.push_back(sc->triangles[i]);
+            sub_id.push_back(i);
+        }
+    if (sub.empty() || sub.size() >= fewer_than) return RT_OK;
+    const int R = sc->ploc_radius > 0 ? std::min(sc->ploc_radius, rtb::PLOC_R_MAX) : rtb::PLOC_R;
+    const int rc = wide_view(ctx, sub.data(), (int)sub.size(), built, R, inflate, sc->collapse_node_cost, v);
+    if (rc == RT_E_HIP) return rc;
+    if (rc == RT_OK)
+        for (int& o : v.orig) o = sub_id[o];  // subset position -> original triangle index
+    else
+        v = HostWide();  // no usable view: the full one serves every ray
+    return RT_OK;
 }
 }  // namespace
 
@@ -767,9 +778,10 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
     HIPC(hipSetDevice(ctx->device));
     const int n = sc->n_triangles;
     HostView hr, ha;
-    std::vector<float4> wide_nodes, wide_tris;
-    std::vector<int> wide_orig;
-    int wide_depth = 0;
+    HostWide wide, unit, prim;
+    // the boxes' inflation: 2^-16 of the scene's coordinate magnitude (>= 20x the slab tests' rounding reach)
+    const float scene_mx = scene_magnitude(sc->triangles, n);
+    const float inflate = std::ldexp(scene_mx, -16);
     int rc = build_view(ctx, sc->bvh, sc->n_nodes, sc->tri_idx, sc->triangles, n, 0.0f, hr);
     if (rc) return rc;
     // the reference tree's child-box faces per axis, sorted (rtd::DScene::faces), uploaded with the scene below
@@ -809,8 +821,7 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
         rc = RT_OK;
     }
     if (own_acc) {
-        // the fast walk's BVH: binned SAH over the same triangles (librt_host.so), boxes inflated by
-        // 2^-16 of the scene's coordinate magnitude (>= 20x the slab tests' rounding reach); or the GPU-built tree
+        // the fast walk's BVH: binned SAH over the same triangles (librt_host.so), boxes inflated; or the GPU-built tree
         rt_bvh_node* nodes = nullptr;
         int nlen = 0;
         int* idx = nullptr;
@@ -828,30 +839,11 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
         } else if (rth_bvh_build(sc->triangles, (size_t)n, RTH_BVH_BINNED_SAH, nullptr, &nodes, &nlen, &idx, nullptr) != RT_OK) {
             return arg_err(ctx, "rt_upload_scene: acceleration BVH build failed");
         }
-        float mx = 16.0f;
-        for (int i = 0; i < n; i++)
-            for (const rt_vec3& c : sc->triangles[i].coords)
-                mx = std::max(mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
-        const float inflate = std::ldexp(mx, -16);
         // the binary fast walk's view (used only without a wide view): not for a GPU-built tree, whose depth is
         // not bounded by the binary walks' 34-entry stack (the reference tree serves instead)
         if (built != RT_ACCEL_GPU) rc = build_view(ctx, nodes, nlen, idx, sc->triangles, n, inflate, ha);
         // ... and its 8-wide quantised form (same inflation, planes rounded outward)
-        uint32_t* words = nullptr;
-        int* order = nullptr;
-        rth_wbvh_info wi{};
-        const auto t_c = std::chrono::steady_clock::now();
-        const bool wide_ok = !rc && rth_wbvh_build_cost(nodes, nlen, idx, sc->triangles, n, inflate,
-                                                        sc->collapse_node_cost, &words, &order, &wi) == RT_OK;
-        ctx->t_collapse += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
-        if (wide_ok && wi.depth <= rtd::WSTACK) {
-            wide_nodes.resize(5 * (size_t)wi.n_nodes);
-            std::memcpy(wide_nodes.data(), words, sizeof(uint32_t) * 20 * (size_t)wi.n_nodes);
-            tri_records(sc->triangles, order, n, wide_tris, wide_orig);
-            wide_depth = wi.depth;
-        }
-        rth_free(words);
-        rth_free(order);
+        if (!rc) (void)collapse_wide(ctx, nodes, nlen, idx, sc->triangles, n, inflate, sc->collapse_node_cost, wide);
         if (built == RT_ACCEL_GPU) {
             std::free(nodes);
             std::free(idx);
@@ -860,7 +852,7 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
             rth_free(idx);
         }
         if (rc) return rc;
-        if (built == RT_ACCEL_GPU && wide_nodes.empty()) {  // too deep for the wide walk's stack: host build instead
+        if (built == RT_ACCEL_GPU && wide.nodes.empty()) {  // too deep for the wide walk's stack: host build instead
             rt_scene s2 = *sc;
             s2.accel = RT_ACCEL_HOST;
             const int r2 = rt_upload_scene(ctx, &s2);
@@ -869,72 +861,12 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
         }
         own_acc = built != RT_ACCEL_GPU;  // (no binary acceleration view for a GPU-built tree)
     }
-    // the unit-direction view (reflection and shadow rays): the same build over the triangles such a ray can hit
-    std::vector<float4> unit_nodes, unit_tris;
-    std::vector<int> unit_orig;
-    int unit_depth = 0, unit_tris_n = 0;
-    if (!wide_nodes.empty()) {
-        std::vector<rt_triangle> sub;
-        std::vector<int> sub_id;
-        for (int i = 0; i < n; i++)
-            if (hittable(sc->triangles[i], 1.0)) {
-                sub.push_back(sc->triangles[i]);
-                sub_id.push_back(i);
-            }
-        if (!sub.empty() && (int)sub.size() < n) {
-            float mx = 16.0f;  // the full view's inflation (all triangles' coordinate magnitude)
-            for (int i = 0; i < n; i++)
-                for (const rt_vec3& c : sc->triangles[i].coords)
-                    mx = std::max(mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
-            const int R = sc->ploc_radius > 0 ? std::min(sc->ploc_radius, rtb::PLOC_R_MAX) : rtb::PLOC_R;
-            rc = wide_view(ctx, sub.data(), (int)sub.size(), built, R, std::ldexp(mx, -16), sc->collapse_node_cost,
-                           unit_nodes, unit_tris, unit_orig, unit_depth);
-            if (rc == RT_E_HIP) return rc;
-            if (rc == RT_OK) {
-                for (int& o : unit_orig) o = sub_id[o];  // subset position -> original triangle index
-                unit_tris_n = (int)sub.size();
-            } else {  // no usable view: the full one serves every ray
-                unit_nodes.clear();
-                unit_tris.clear();
-                unit_orig.clear();
-                unit_depth = 0;
-            }
-            rc = RT_OK;
-        }
-    }
-    // the primary view: the same build over the triangles a direction of length <= PRIMARY_D can hit (only when
-    // that leaves out at least 2 % of them)
-    std::vector<float4> prim_nodes, prim_tris;
-    std::vector<int> prim_orig;
-    int prim_depth = 0, prim_tris_n = 0;
-    if (!wide_nodes.empty()) {
-        std::vector<rt_triangle> sub;
-        std::vector<int> sub_id;
-        for (int i = 0; i < n; i++)
-            if (hittable(sc->triangles[i], PRIMARY_D)) {
-                sub.push_back(sc->triangles[i]);
-                sub_id.push_back(i);
-            }
-        if (!sub.empty() && sub.size() < (size_t)n - (size_t)n / 50) {
-            float mx = 16.0f;
-            for (int i = 0; i < n; i++)
-                for (const rt_vec3& c : sc->triangles[i].coords)
-                    mx = std::max(mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
-            const int R = sc->ploc_radius > 0 ? std::min(sc->ploc_radius, rtb::PLOC_R_MAX) : rtb::PLOC_R;
-            rc = wide_view(ctx, sub.data(), (int)sub.size(), built, R, std::ldexp(mx, -16), sc->collapse_node_cost,
-                           prim_nodes, prim_tris, prim_orig, prim_depth);
-            if (rc == RT_E_HIP) return rc;
-            if (rc == RT_OK) {
-                for (int& o : prim_orig) o = sub_id[o];
-                prim_tris_n = (int)sub.size();
-            } else {
-                prim_nodes.clear();
-                prim_tris.clear();
-                prim_orig.clear();
-                prim_depth = 0;
-            }
-            rc = RT_OK;
-        }
+    // the unit-direction view (reflection and shadow rays): the same build over the triangles such a ray can hit; the
+    // primary view: over those a direction of length <= PRIMARY_D can hit (only when that leaves out at least 2 % of
+    // them). Both with the full view's inflation.
+    if (!wide.nodes.empty()) {
+        if ((rc = subset_view(ctx, sc, 1.0, (size_t)n, built, inflate, unit))) return rc;
+        if ((rc = subset_view(ctx, sc, PRIMARY_D, (size_t)n - (size_t)n / 50, built, inflate, prim))) return rc;
     }
     const float build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
     // materials: distinct (ks, kd, kr) triples of triangle_t (the reference stores them per triangle)
@@ -968,30 +900,15 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
     if ((rc = upload_view(ctx, hr, ctx->ref)) || (own_acc && (rc = upload_view(ctx, ha, ctx->acc))) ||
         (rc = upload(ctx, &ctx->d_shade, shade)) || (rc = upload(ctx, &ctx->d_mats, mats)) ||
         (rc = upload(ctx, &ctx->d_lights, lights)) || (rc = upload(ctx, &ctx->d_faces, all_faces)) ||
-        (!wide_nodes.empty() && ((rc = upload(ctx, &ctx->wide_nodes, wide_nodes)) ||
-                                 (rc = upload(ctx, &ctx->wide_tris, wide_tris)) ||
-                                 (rc = upload(ctx, &ctx->wide_orig, wide_orig)))) ||
-        (!unit_nodes.empty() && ((rc = upload(ctx, &ctx->unit_nodes, unit_nodes)) ||
-                                 (rc = upload(ctx, &ctx->unit_tris, unit_tris)) ||
-                                 (rc = upload(ctx, &ctx->unit_orig, unit_orig)))) ||
-        (!prim_nodes.empty() && ((rc = upload(ctx, &ctx->prim_nodes, prim_nodes)) ||
-                                 (rc = upload(ctx, &ctx->prim_tris, prim_tris)) ||
-                                 (rc = upload(ctx, &ctx->prim_orig, prim_orig))))) {
+        (rc = upload_wide(ctx, wide, ctx->wide)) || (rc = upload_wide(ctx, unit, ctx->unit)) ||
+        (rc = upload_wide(ctx, prim, ctx->prim))) {
         free_scene(ctx);
         return rc;
     }
     for (int a = 0; a < 3; a++) ctx->faces[a].swap(faces[a]);
-    ctx->wide_n = (int)(wide_nodes.size() / 5);
-    ctx->wide_depth = wide_depth;
-    ctx->unit_n = (int)(unit_nodes.size() / 5);
-    ctx->unit_depth = unit_depth;
-    ctx->unit_tris_n = unit_nodes.empty() ? 0 : unit_tris_n;
-    ctx->prim_n = (int)(prim_nodes.size() / 5);
-    ctx->prim_depth = prim_depth;
-    ctx->prim_tris_n = prim_nodes.empty() ? 0 : prim_tris_n;
     ctx->n_lights = sc->n_lights;
     ctx->n_tris = n;
-    ctx->pk_ok = std::max(ctx->wide_n, std::max(ctx->unit_n, ctx->prim_n)) <= rtd::WIDE_MAX_NODES &&
+    ctx->pk_ok = std::max(ctx->wide.n, std::max(ctx->unit.n, ctx->prim.n)) <= rtd::WIDE_MAX_NODES &&
                  !(ctx->flags & RT_FLAG_UNPACKED_STACK);
     ctx->tq_ok = n < rtd::TQ_MAX_TRIS && !(ctx->flags & RT_FLAG_UNPACKED_TRIS);
     ctx->amb[0] = sc->amb.x;
@@ -999,20 +916,17 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
     ctx->amb[2] = sc->amb.z;
     ctx->has_scene = true;
     ctx->scene_gen++;
-    ctx->scene_mx = 16.0f;  // (as the inflation above: max(16, max |coordinate|))
-    for (int i = 0; i < n; i++)
-        for (const rt_vec3& c : sc->triangles[i].coords)
-            ctx->scene_mx = std::max(ctx->scene_mx, std::max(std::fabs(c.x), std::max(std::fabs(c.y), std::fabs(c.z))));
+    ctx->scene_mx = scene_mx;
     ctx->info = rt_scene_info{};
     ctx->info.n_triangles = n;
     ctx->info.n_lights = sc->n_lights;
-    ctx->info.wide_nodes = ctx->wide_n;
-    ctx->info.wide_depth = wide_depth;
-    ctx->info.unit_triangles = ctx->unit_tris_n;
-    ctx->info.unit_nodes = ctx->unit_n;
-    ctx->info.unit_depth = unit_depth;
-    ctx->info.primary_triangles = ctx->prim_tris_n;
-    ctx->info.primary_nodes = ctx->prim_n;
+    ctx->info.wide_nodes = ctx->wide.n;
+    ctx->info.wide_depth = ctx->wide.depth;
+    ctx->info.unit_triangles = ctx->unit.tris_n;
+    ctx->info.unit_nodes = ctx->unit.n;
+    ctx->info.unit_depth = ctx->unit.depth;
+    ctx->info.primary_triangles = ctx->prim.tris_n;
+    ctx->info.primary_nodes = ctx->prim.n;
     ctx->info.accel_built = built;
     ctx->info.build_ms = build_ms;
     ctx->info.gpu_build_ms = gpu_ms;
@@ -1033,6 +947,10 @@ extern "C" int rt_get_scene_info(rt_ctx* ctx, rt_scene_info* info) {
 }
 
 namespace {
+
+// The kernels are built for MAXB = 4 bounce levels (the reference's BOUNCES) and for 8: fn<MAXB>(...) of the build that
+// serves a frame's bounces.
+#define FOR_MAXB(bounces, fn, ...) ((bounces) <= 4 ? fn<4>(__VA_ARGS__) : fn<8>(__VA_ARGS__))
 
 // resident workgroups per CU of a persistent kernel (occupancy API, capped at 8)
 template <class K>
@@ -1100,6 +1018,23 @@ bool pbl_fits(const rtd::KArgs& A, int device, int shp = 0) {
                                                         pbl_bytes<MAXB>(A, shp)) == hipSuccess &&
            per_cu >= 4;
 }
+bool pbl_fits(const rtd::KArgs& A, int device, int shp) { return FOR_MAXB(A.bounces, pbl_fits, A, device, shp); }
+
+// k_tiles (RT_KERNEL_STRICT): one thread per pixel of a 16x16 tile, the reference's walk
+template <int MAXB>
+KFn tiles_kernel_of(bool count) {
+    return count ? rtd::k_tiles<MAXB, true, true> : rtd::k_tiles<MAXB, true, false>;
+}
+KFn tiles_kernel(int bounces, bool count) { return FOR_MAXB(bounces, tiles_kernel_of, count); }
+
+// k_coop (rt_coop.hpp): G = 2 or 4 lanes per ray; one wave per tile of 64 / G pixels
+template <int MAXB>
+KFn coop_kernel_of(int G, bool count) {
+    using rtd::k_coop;
+    if (G == 2) return count ? k_coop<MAXB, true, 2, 3, false, true> : k_coop<MAXB, false, 2, 3, false, true>;
+    return count ? k_coop<MAXB, true, 4, 3, false, true> : k_coop<MAXB, false, 4, 3, false, true>;
+}
+KFn coop_kernel(int bounces, int G, bool count) { return FOR_MAXB(bounces, coop_kernel_of, G, count); }
 
 // k_persist (the persistent one-lane-per-path kernel) in configuration `variant`, and its dynamic LDS:
 //   RT_VARIANT_PERSIST   <= 168 VGPRs (3 waves per SIMD), path levels in registers (spp = 1: packed triangle tests);
@@ -1113,8 +1048,8 @@ bool pbl_fits(const rtd::KArgs& A, int device, int shp = 0) {
 // a tile trace (A.tile_trace: the hybrid launch's measuring frame, PRT_TILE_TRACE) runs the 3-wave build with
 // per-tile timestamps.
 template <int MAXB>
-KFn persist_kernel(const rtd::KArgs& A, int variant, bool count, int device, size_t& dyn, bool pk_ok, bool tq_ok,
-                   unsigned* build = nullptr) {
+KFn persist_kernel_of(const rtd::KArgs& A, int variant, bool count, int device, size_t& dyn, bool pk_ok, bool tq_ok,
+                      unsigned* build) {
     dyn = 0;
     unsigned bd = 0;  // rt_launch_info.build of the instantiation returned (RT_BUILD_*)
     struct Report {
@@ -1170,29 +1105,48 @@ KFn persist_kernel(const rtd::KArgs& A, int variant, bool count, int device, siz
     return count ? rtd::k_persist<MAXB, false, true, true, 3, false, true> : rtd::k_persist<MAXB, false, false, true, 3, false, true>;
 }
 
+KFn persist_kernel(const rtd::KArgs& A, int variant, bool count, int device, size_t& dyn, bool pk_ok, bool tq_ok,
+                   unsigned* build = nullptr) {
+    return FOR_MAXB(A.bounces, persist_kernel_of, A, variant, count, device, dyn, pk_ok, tq_ok, build);
+}
+
 // `cap`: workgroups per CU at most (0: the occupancy limit); the grid never exceeds the tiles / 4.
-template <int MAXB>
 void launch_paths(const rtd::KArgs& A, int variant, bool count, int device, hipStream_t s, int cap, bool pk_ok,
                   bool tq_ok, unsigned* build = nullptr) {
     size_t dyn = 0;
-    const KFn k = persist_kernel<MAXB>(A, variant, count, device, dyn, pk_ok, tq_ok, build);
+    const KFn k = persist_kernel(A, variant, count, device, dyn, pk_ok, tq_ok, build);
     const int blocks = std::max(1, std::min(resident(k, device, cap > 0 ? cap : 8, dyn), (A.n_tiles * A.n_frames + 3) / 4));
     k<<<blocks, rtd::BLOCK, dyn, s>>>(with_slots(A, dyn));
 }
 
 rtd::DBvh dview(const DevView& v) { return rtd::DBvh{v.nodes, v.leaves, v.tris, v.orig, v.root}; }
 
-// k_coop (rt_coop.hpp): G = 2 or 4 lanes per ray; one wave per tile of 64 / G pixels
-template <int MAXB>
-KFn coop_kernel(int G, bool count) {
-    using rtd::k_coop;
-    if (G == 2) return count ? k_coop<MAXB, true, 2, 3, false, true> : k_coop<MAXB, false, 2, 3, false, true>;
-    return count ? k_coop<MAXB, true, 4, 3, false, true> : k_coop<MAXB, false, 4, 3, false, true>;
+// the uploaded scene as the kernels take it (the renders' KArgs::s, the ray queries' QArgs::s)
+rtd::DScene scene_args(const rt_ctx* ctx) {
+    rtd::DScene s;
+    std::memset(&s, 0, sizeof s);
+    s.ref = dview(ctx->ref);
+    s.acc = ctx->acc.nodes ? dview(ctx->acc) : s.ref;
+    s.wide = ctx->wide.view();
+    s.unit = ctx->unit.view();
+    s.prim = ctx->prim.view();
+    s.shade = ctx->d_shade;
+    s.mats = ctx->d_mats;
+    s.lights = ctx->d_lights;
+    s.n_lights = ctx->n_lights;
+    s.amb_x = ctx->amb[0];
+    s.amb_y = ctx->amb[1];
+    s.amb_z = ctx->amb[2];
+    s.faces = ctx->d_faces;  // (rt_kernels.hpp degenerate_ok)
+    s.ref_path = ctx->ref.path;  // (rt_kernels.hpp ref_reaches)
+    s.n_tris = ctx->n_tris;
+    for (int a = 0; a < 3; a++) s.n_face[a] = (int)ctx->faces[a].size();
+    return s;
 }
-// never more workgroups than tiles / 4
-template <int MAXB>
+
+// k_coop over the whole frame: never more workgroups than tiles / 4
 int launch_group(const rtd::KArgs& A, int g, bool count, int device, hipStream_t s, int cap) {
-    const KFn k = coop_kernel<MAXB>(g, count);
+    const KFn k = coop_kernel(A.bounces, g, count);
     const int blocks = std::max(1, std::min(resident(k, device, cap), (A.n_tiles * A.n_frames + 3) / 4));
     k<<<blocks, rtd::BLOCK, 0, s>>>(A);
     return RT_OK;
@@ -1201,52 +1155,8 @@ int launch_group(const rtd::KArgs& A, int g, bool count, int device, hipStream_t
 }  // namespace
 
 namespace {
-// Centre-out order of a tx x ty tile grid (the persistent kernels' default dealing order), by runs of SUPER tiles
-// side by side in a row: an 8x8 tile of 4-B pixels stores 32-B row pieces, so SUPER = 4 neighbouring tiles fill
-// whole 128-B lines, and dealt back to back they are written while the line is still in the XCD's L2 (a line
-// left partly written leaves L2 once per piece: WRITE_SIZE).
-constexpr int SUPER = 4;
-std::vector<int> centre_out(int tx, int ty) {
-    const int n = tx * ty;
-    std::vector<int> ord(n);
-    for (int i = 0; i < n; i++) ord[i] = i;
-    const float cx = 0.5f * tx, cy = 0.5f * ty;
-    auto d2 = [&](int t) {
-        const int x0 = (t % tx) / SUPER * SUPER, x1 = std::min(tx, x0 + SUPER);
-        const float dx = 0.5f * (x0 + x1) - cx, dy = t / tx + 0.5f - cy;
-        return dx * dx + dy * dy;
-    };
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
-        const float da = d2(a), db = d2(b);
-        if (da != db) return da < db;
-        return a / tx != b / tx ? a / tx < b / tx : a < b;  // a run's tiles together, left to right
-    });
-    return ord;
-}
-
-// XCD-aware layout of a dealing order (rtd::next_item): 9 region offsets into the tile part, then the tiles of
-// region 0..7, each region in the order's order. mode 1: 8 bands of tile rows, 2: 8 bands of tile columns,
-// 3: 4 x 2 blocks.
-std::vector<int> region_layout(const std::vector<int>& ord, int tx, int ty, int mode) {
-    std::vector<int> dev(9 + ord.size());
-    int at = 9;
-    for (int r = 0; r < 8; r++) {
-        dev[r] = at;
-        for (int t : ord) {
-            const int reg = mode == 1 ? (t / tx) * 8 / ty : mode == 2 ? (t % tx) * 8 / tx
-                                                                    : (t % tx) * 4 / tx + 4 * ((t / tx) * 2 / ty);
-            if (reg == r) dev[at++] = t;
-        }
-    }
-    dev[8] = at;
-    for (int r = 0; r <= 8; r++) dev[r] -= 9;  // offsets into the order part
-    return dev;
-}
-
-template <int MAXB>
-int launch_hybrid(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build = nullptr);  // below
-template <int MAXB>
-int launch_hybrid_fb(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build);  // below
+using rtl::centre_out;
+using rtl::region_layout;
 
 // A frame batch's cameras to d_cams when they differ from the set it holds. The copy runs in stream order (after the
 // renders in flight, which read the old set) from a ring of pinned slots; only a slot whose previous copy has not
@@ -1282,85 +1192,49 @@ int upload_cams(rt_ctx* ctx, const rt_camera* cams, int n_frames) {
     return RT_OK;
 }
 
-// rt_render / rt_render_frames: n_frames frames of the same shape (cameras cams[0..n_frames-1]); outputs
-// [n_frames][n_rows][width]... Persistent fast configurations trace the whole batch in ONE launch (frames'
-// tiles interleaved in the dealing order); other kernels launch once per frame.
-int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_frame* f, const rt_outputs* out) {
-    if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_render: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!cams || !f) return arg_err(ctx, "rt_render: null camera/frame");
-    if (n_frames < 1 || n_frames > 4096) return arg_err(ctx, "rt_render_frames: n_frames must be 1..4096");
-    const rt_camera* cam = cams;
-    const int rb = f->row_block > 1 ? f->row_block : 1;
-    const int fs = f->frame_shift;
-    if (f->width <= 0 || f->height <= 0 || f->row_stride <= 0 || f->n_rows <= 0 || f->row_offset < 0 ||
-        f->row_block < 0 || fs < 0 || (f->n_rows > rb && f->row_stride < rb) ||
-        (fs == 0 && (long long)f->row_offset + (long long)((f->n_rows - 1) / rb) * f->row_stride +
-                            (f->n_rows - 1) % rb >= f->height) ||
-        (fs > 0 && (f->row_offset >= f->row_stride || f->row_offset >= f->height ||
-                    (long long)f->n_rows > (long long)f->row_stride * f->height)))
-        return arg_err(ctx, "rt_render: rows outside the frame");
-    if (fs > 0 && f->kernel != RT_KERNEL_FAST && f->kernel != RT_KERNEL_AUTO)
-        return arg_err(ctx, "rt_render: frame_shift needs RT_KERNEL_FAST");
-    if (f->bounces < 1 || f->bounces > 8) return arg_err(ctx, "rt_render: bounces must be 1..8");
-    int g = 1;
-    while (g * g < f->spp) g++;
-    if (f->spp < 1 || g * g != f->spp || g > 16) return arg_err(ctx, "rt_render: spp must be a square 1..256");
-    if (f->kernel < RT_KERNEL_AUTO || f->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_render: bad kernel");
-    if (f->spp > 1 && (f->width > 65535 || f->n_rows > 65535))  // (k_persist's multi-sample slots pack x and the row)
-        return arg_err(ctx, "rt_render: spp > 1 frames are at most 65535 pixels wide and 65535 rows high");
-    // (variants 3, 6, 7, 8, 9, 10, 12, 14 -- the split pipeline, k_coop<8>, k_fan, k_chain, k_pool, k_relay, k_stream
-    // -- measured slower than k_persist and were removed: refused)
-    const bool known = f->variant == RT_VARIANT_DEFAULT || f->variant == RT_VARIANT_PERSIST ||
-                       f->variant == RT_VARIANT_PERSIST4 || f->variant == RT_VARIANT_COOP2 ||
-                       f->variant == RT_VARIANT_COOP4 || f->variant == RT_VARIANT_HYBRID ||
-                       f->variant == RT_VARIANT_SHPOOL || f->variant == RT_VARIANT_SHDEFER;
-    if (!known || f->hot_pct < 0 || f->hot_pct > 100 || f->hot_kernel < RT_HOT_COOP4 || f->hot_kernel > RT_HOT_COOP2 ||
-        f->tune < 0 || f->tune > 1 ||
-        f->waves_cap < 0 || f->waves_cap > 8 || f->dealing < RT_DEAL_DEFAULT || f->dealing > RT_DEAL_ROW_MAJOR ||
-        f->regroup < 0 || f->regroup > 64)
-        return arg_err(ctx, "rt_render: bad launch configuration (variant / tune / waves_cap / dealing / regroup)");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t pixels = (size_t)f->width * f->n_rows;  // per frame
-    const size_t all_px = pixels * (size_t)n_frames;
-    if (all_px > (size_t)INT_MAX)  // (the kernels index a launch's output pixels with 32-bit integers)
-        return arg_err(ctx, "rt_render: the launch's frames x pixels exceed 2^31 - 1");
-    float* rgb = out ? out->rgb : nullptr;
-    unsigned* bgra = out ? out->bgra : nullptr;
-    if (!rgb && !bgra) {  // a quantised-only frame writes no f32 pixels at all
-        if (ctx->rgb_cap < all_px) {
-            if (ctx->d_rgb_own) HIPC(hipFree(ctx->d_rgb_own));
-            ctx->d_rgb_own = nullptr;
-            ctx->rgb_cap = 0;
-            HIPC(hipMalloc((void**)&ctx->d_rgb_own, sizeof(float) * 3 * all_px));
-            ctx->rgb_cap = all_px;
-        }
-        rgb = ctx->d_rgb_own;
-    }
+// One render call (render_batch): what its steps share
+struct Launch {
+    const rt_frame* f = nullptr;
+    const rt_camera* cams = nullptr;
+    int n_frames = 1;
+    int kernel = RT_KERNEL_FAST;  // rt_frame.kernel, RT_KERNEL_AUTO resolved
+    bool count = false;           // RT_FLAG_COUNTERS: the kernels' counting builds
     rtd::KArgs A;
+    // Tile dealing order of the persistent kernels: centre-out (default). The frame ends when the slowest
+    // tile does (PRT_TILE_TRACE: 8x8 tiles range from 2 us to ~1.9 ms; expensive ones are deep reflection
+    // chains, usually on the object in view); dealing from the centre starts them first (bench frame
+    // -7 %). RT_DEAL_ROW_MAJOR: row-major.
+    bool centre_out = false;
+    int xcd_mode = 0;  // the order's XCD-region layout (rtl::xcd_mode_of), and that layout on the device (null: none)
+    const int *region_off = nullptr, *region_order = nullptr;
+    rtl::Caps caps;       // what the scene and the frame allow (launch_caps)
+    rt_launch_info li{};  // what this render runs (rt_get_launch_info)
+};
+
+// the context's own f32 pixels, for a call that names no output (a quantised-only frame writes no f32 pixels at all)
+int own_rgb(rt_ctx* ctx, size_t all_px, float*& rgb) {
+    if (ctx->rgb_cap < all_px) {
+        if (ctx->d_rgb_own) HIPC(hipFree(ctx->d_rgb_own));
+        ctx->d_rgb_own = nullptr;
+        ctx->rgb_cap = 0;
+        HIPC(hipMalloc((void**)&ctx->d_rgb_own, sizeof(float) * 3 * all_px));
+        ctx->rgb_cap = all_px;
+    }
+    rgb = ctx->d_rgb_own;
+    return RT_OK;
+}
+
+// the kernel arguments of the call's first frame: scene, camera, rows, outputs
+void fill_args(const rt_ctx* ctx, Launch& L, const rt_outputs* out, float* rgb, unsigned* bgra, int spp_grid) {
+    const rt_frame* f = L.f;
+    rtd::KArgs& A = L.A;
     std::memset(&A, 0, sizeof A);
-    A.s.ref = dview(ctx->ref);
-    A.s.acc = ctx->acc.nodes ? dview(ctx->acc) : A.s.ref;
-    A.s.wide = rtd::DWide{ctx->wide_nodes, ctx->wide_tris, ctx->wide_orig, ctx->wide_n};
-    A.s.unit = rtd::DWide{ctx->unit_nodes, ctx->unit_tris, ctx->unit_orig, ctx->unit_n};
+    A.s = scene_args(ctx);
     // the primary view when every primary direction of every frame of the launch is short enough for it
-    bool prim_ok = ctx->prim_nodes != nullptr;
-    for (int i = 0; i < n_frames && prim_ok; i++) prim_ok = primary_dmax(cams + i, f->width, f->height) <= PRIMARY_D;
-    if (prim_ok) A.s.prim = rtd::DWide{ctx->prim_nodes, ctx->prim_tris, ctx->prim_orig, ctx->prim_n};
-    A.s.shade = ctx->d_shade;
-    A.s.mats = ctx->d_mats;
-    A.s.lights = ctx->d_lights;
-    A.s.n_lights = ctx->n_lights;
-    A.s.amb_x = ctx->amb[0];
-    A.s.amb_y = ctx->amb[1];
-    A.s.amb_z = ctx->amb[2];
-    A.s.faces = ctx->d_faces;  // (rt_kernels.hpp degenerate_ok)
-    A.s.ref_path = ctx->ref.path;  // (rt_kernels.hpp ref_reaches)
-    A.s.n_tris = ctx->n_tris;
-    for (int a = 0; a < 3; a++) A.s.n_face[a] = (int)ctx->faces[a].size();
+    bool prim_ok = ctx->prim.nodes != nullptr;
+    for (int i = 0; i < L.n_frames && prim_ok; i++) prim_ok = primary_dmax(L.cams + i, f->width, f->height) <= PRIMARY_D;
+    if (!prim_ok) A.s.prim = rtd::DWide{nullptr, nullptr, nullptr, 0};
+    const rt_camera* cam = L.cams;
     const rt_vec3* cv[4] = {&cam->pos, &cam->ul, &cam->inc_x, &cam->inc_y};
     float* dst[4] = {A.pos, A.ul, A.ix, A.iy};
     for (int i = 0; i < 4; i++) {
@@ -1372,12 +1246,12 @@ int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_fram
     A.H = f->height;
     A.row_offset = f->row_offset;
     A.row_stride = f->row_stride;
-    A.row_block = rb;
-    A.frame_shift = fs;
+    A.row_block = f->row_block > 1 ? f->row_block : 1;
+    A.frame_shift = f->frame_shift;
     A.n_rows = f->n_rows;
     A.bounces = f->bounces;
     A.spp = f->spp;
-    A.spp_grid = g;
+    A.spp_grid = spp_grid;
     A.rgb = rgb;
     A.bgra = bgra;
     A.hit = out ? out->hit : nullptr;
@@ -1388,8 +1262,641 @@ int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_fram
     A.tiles_x = (f->width + 7) / 8;
     A.n_tiles = A.tiles_x * ((f->n_rows + 7) / 8);
     A.tiles_x8 = A.tiles_x;
-    const int kernel = f->kernel == RT_KERNEL_AUTO ? RT_KERNEL_FAST : f->kernel;
-    if (n_frames > 1 && kernel != RT_KERNEL_FAST) {  // one launch per frame, outputs at frame offsets
+}
+
+// the fast kernels' per-wave buffers, allocated on the first fast render
+int walk_buffers(rt_ctx* ctx) {
+    if (ctx->d_pathbuf && ctx->d_gstack && ctx->d_lanebuf) return RT_OK;
+    // (each buffer its own check: a failed allocation of one of them leaves the others, and the next render
+    // retries the missing one instead of launching with a null buffer)
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    const size_t waves = (size_t)cus * 8 * (rtd::BLOCK / 64);  // <= 8 workgroups per CU (resident() cap)
+    // path buffer of the PB kernels: every resident wave, MAXB <= 8 levels
+    if (!ctx->d_pathbuf) HIPC(hipMalloc((void**)&ctx->d_pathbuf, sizeof(float4) * waves * 8 * 64));
+    // DYN kernels' binary-walk stacks: STACK ints per lane of every resident workgroup (<= 8 per CU)
+    if (!ctx->d_gstack) HIPC(hipMalloc((void**)&ctx->d_gstack, sizeof(int) * (size_t)cus * 8 * rtd::STACK * rtd::BLOCK));
+    // the multi-sample builds' per-lane slots (the running sum and the pixel between samples): every resident lane
+    if (!ctx->d_lanebuf) HIPC(hipMalloc((void**)&ctx->d_lanebuf, sizeof(float4) * (size_t)cus * 8 * rtd::BLOCK));
+    return RT_OK;
+}
+
+// A tile list of the context's cache (rt_ctx::orders), made and copied to the device on its first use
+template <class Make>
+int cached_list(rt_ctx* ctx, long long key, Make make, const int*& list) {
+    auto it = ctx->orders.find(key);
+    if (it == ctx->orders.end()) {
+        const std::vector<int> v = make();
+        int* d = nullptr;
+        HIPC(hipMalloc((void**)&d, sizeof(int) * v.size()));
+        HIPC(hipMemcpy(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice));
+        it = ctx->orders.emplace(key, d).first;
+    }
+    list = it->second;
+    return RT_OK;
+}
+// the dealing order of a tx x ty tile grid on the device: one cached permutation per grid (null: row-major)
+int order_for(rt_ctx* ctx, const Launch& L, int tx, int ty, const int*& ord) {
+    ord = nullptr;
+    if (!L.centre_out) return RT_OK;
+    return cached_list(ctx, ((long long)tx << 32) | (unsigned)ty, [&] { return centre_out(tx, ty); }, ord);
+}
+// the launch's tile order, and its XCD-region layout (device layout: 9 region offsets, then the concatenated regions'
+// tiles)
+int tile_orders(rt_ctx* ctx, Launch& L) {
+    const rt_frame* f = L.f;
+    const int tx = L.A.tiles_x, ty = L.A.n_tiles / L.A.tiles_x;
+    L.centre_out = L.kernel == RT_KERNEL_FAST && f->dealing != RT_DEAL_ROW_MAJOR;
+    if (int rc = order_for(ctx, L, tx, ty, L.A.tile_order)) return rc;
+    L.xcd_mode = rtl::xcd_mode_of(f->dealing, L.n_frames, f->row_offset == 0 && f->n_rows == f->height);
+    if (!(L.centre_out && L.xcd_mode >= 1 && L.xcd_mode <= 3)) return RT_OK;
+    const long long key = ((long long)L.xcd_mode << 58) | ((long long)tx << 32) | (unsigned)ty;
+    if (int rc = cached_list(ctx, key, [&] { return region_layout(centre_out(tx, ty), tx, ty, L.xcd_mode); }, L.region_off))
+        return rc;
+    L.region_order = L.region_off + 9;
+    return RT_OK;
+}
+
+// RT_KERNEL_FAST launch configurations (rt_frame.variant; every one renders the same bits):
+//   PERSIST / PERSIST4  k_persist, one lane per pixel path, walks in lockstep, 8x8 tiles;
+//   SHPOOL              k_persist at 4 waves with each level's shadow rays walked as a per-wave pool;
+//   COOP2/4             k_coop (rt_coop.hpp): G lanes per ray, 64/G-pixel tiles — shorter chains per tile,
+//                       which is what a frame split over many GPUs (few tiles per wave) is bound by;
+//   HYBRID              single frames: the costliest tiles through k_coop on a second stream (§3e).
+// What this launch's scene and frame allow of them (rtl::resolve_variant)
+rtl::Caps launch_caps(const rt_ctx* ctx, const Launch& L) {
+    rtl::Caps c;
+    c.wide = L.kernel == RT_KERNEL_FAST && ctx->wide.n > 0;
+    // the shadow pool: 1..32 lights (a 32-bit visibility word per pixel) and the LDS path buffer at 4 workgroups per CU
+    c.shp_ok = c.wide && ctx->n_lights >= 1 && ctx->n_lights <= 32 && ctx->pk_ok && ctx->tq_ok &&
+               pbl_fits(L.A, ctx->device, 1);
+    c.shd_ok = c.shp_ok && ctx->n_lights <= 8 && pbl_fits(L.A, ctx->device, 2);
+    c.tile_trace = L.A.tile_trace != nullptr;
+    c.n_lights = ctx->n_lights;
+    c.n_frames = L.n_frames;
+    c.frame_shift = L.f->frame_shift;
+    c.spp = L.f->spp;
+    return c;
+}
+
+bool tune_log() {
+    const char* l = std::getenv("PRT_TUNE_LOG");
+    return l && std::atoi(l) == 1;
+}
+
+// The default rule for frame batches and spp > 1 where the shadow pool can run: measured, not guessed. Whether the
+// pool pays depends on the scene (dragon 20-frame batches 0.708 -> 0.666 ms per frame; two_cars 4K 1.881 vs 1.917,
+// car_boxed 0.868 vs 0.902), so the first launches of a shape try PERSIST4 and SHPOOL ROUNDS times each (their own
+// HIP events, read by a query once the last has run) and the faster per frame renders from then on. A context with
+// traversal counters never tries (the counters of a trial would be another kernel's): it keeps the static rule.
+int batch_rule_pick(rt_ctx* ctx, Launch& L, int& mode) {
+    const rt_frame* f = L.f;
+    const rtl::ShapeKey key = rtl::batch_key(ctx->scene_gen, *f, L.n_frames);
+    rt_ctx::BatchRule* br = nullptr;
+    for (auto& b : ctx->brules)
+        if (b.key == key) br = &b;
+    if (!br) {
+        if (ctx->brules.size() >= 16) ctx->brules.erase(ctx->brules.begin());
+        ctx->brules.emplace_back();
+        br = &ctx->brules.back();
+        br->key = key;
+    }
+    rt_ctx::BatchRule& b = *br;
+    constexpr int nc = 2, R = rtl::BATCH_ROUNDS;
+    const int cand[nc] = {RT_VARIANT_PERSIST4, rtl::pool_v(L.caps)};
+    int pick = -1;
+    if (b.choice < 0) {
+        pick = rtl::next_trial(&b.launch[0][0], nc, R, true, ctx->launches);
+        if (pick < 0) {  // every trial enqueued: decide once the last has run (a query, never a wait)
+            const long long last = rtl::latest_trial(&b.launch[0][0], nc, R);
+            const hipError_t q = hipEventQuery(ctx->ev1s[last % rt_ctx::NEV]);
+            if (q == hipSuccess) {
+                float t[nc * R], ms[nc];
+                for (int c = 0; c < nc; c++)
+                    for (int r = 0; r < R; r++) {
+                        const int sl = (int)(b.launch[c][r] % rt_ctx::NEV);
+                        HIPC(hipEventElapsedTime(&t[c * R + r], ctx->ev0s[sl], ctx->ev1s[sl]));
+                    }
+                b.choice = rtl::batch_decide(t, nc, ms);
+                if (tune_log())
+                    std::fprintf(stderr, "[prt batch] %dx%d f%d spp%d: persist4 %.3f ms, %s %.3f ms -> %s\n",
+                                 f->width, f->n_rows, L.n_frames, f->spp, ms[0], variant_name(cand[1]), ms[1],
+                                 variant_name(cand[b.choice]));
+            } else if (q != hipErrorNotReady) {
+                return fail(ctx, q, "rt_render: batch rule trials");
+            } else {
+                (void)hipGetLastError();  // not an error: the trials are still running
+            }
+        }
+    }
+    if (b.choice >= 0) {
+        mode = cand[b.choice];
+    } else {
+        mode = pick >= 0 ? cand[pick] : rtl::batch_default(L.caps);
+        L.li.trial = 1;
+        L.li.settled = 0;
+    }
+    return RT_OK;
+}
+
+// RT_VARIANT_HYBRID: what this single frame runs. The state is keyed by the frame's SHAPE, not its camera (a
+// walkthrough moves it every frame). The first frame of a shape measures: k_persist with per-tile times, copied to
+// pinned host memory behind it. Once they have arrived (an event query, never a wait) the tile lists of every
+// candidate are built and copied in stream order, and the next frames try the candidates ROUNDS times each,
+// timed by their own HIP events; when the last trial has finished (a query) the fastest median renders from then
+// on (PRT_TUNE_LOG=1 prints them). Every REFRESH frames of the shape a measuring frame renews the tile lists for
+// a moving camera (the choice stays). While a measurement or the trials are in flight, a frame runs the static
+// rule's whole-frame kernel. rt_frame.hot_pct > 0 fixes the threshold (no trials).
+// kind 0: measuring frame; 1: whole-frame variant c; 2: hybrid candidate c's launch (lists at ctx->hy)
+struct Pick {
+    int kind, c;
+};
+
+// has the work before event e run? A query, never a wait
+hipError_t in_flight(hipEvent_t e, bool& done) {
+    const hipError_t q = hipEventQuery(e);
+    done = q == hipSuccess;
+    if (q == hipErrorNotReady) {
+        (void)hipGetLastError();  // not an error: still running
+        return hipSuccess;
+    }
+    return q;
+}
+
+// A new shape (no measurement in flight writes h_tr, no frame of the old shape runs now): its key, buffers for its
+// tiles, and every piece of the old shape's state reset -- it is measured next
+int hybrid_new_shape(rt_ctx* ctx, const rtl::ShapeKey& key, size_t n_tiles) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    h.key = key;
+    h.choice = -1;
+    h.n_tiles = n_tiles;
+    if (h.tr_cap < h.n_tiles) {
+        if (h.d_tr) (void)hipFree(h.d_tr);
+        if (h.h_tr) (void)hipHostFree(h.h_tr);
+        h.d_tr = h.h_tr = nullptr;
+        h.tr_cap = 0;
+        hipError_t e = hipMalloc((void**)&h.d_tr, sizeof(unsigned long long) * 4 * h.n_tiles);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h.h_tr, sizeof(unsigned long long) * 4 * h.n_tiles,
+                                               hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid tile times");
+        h.tr_cap = h.n_tiles;
+    }
+    if (h.fb_cap < h.n_tiles) {  // the feedback's buffers (rt_feedback.hpp)
+        if (h.fb_pending) (void)hipEventSynchronize(h.fb_ev);
+        if (h.d_cost) (void)hipFree(h.d_cost);
+        if (h.d_fb) (void)hipFree(h.d_fb);
+        if (h.d_info) (void)hipFree(h.d_info);
+        h.d_cost = nullptr;
+        h.d_fb = nullptr;
+        h.d_info = nullptr;
+        h.fb_cap = 0;
+        hipError_t e = hipMalloc((void**)&h.d_cost, sizeof(unsigned) * 2 * (h.n_tiles + 1));
+        if (e == hipSuccess) e = hipMalloc((void**)&h.d_fb, sizeof(int) * (5 * h.n_tiles + 13 + rtd::FB_G * (rtd::FB_TK + 3)));
+        if (e == hipSuccess) e = hipMalloc((void**)&h.d_info, h.n_tiles);
+        if (e == hipSuccess && !h.h_fb_cnt) e = hipHostMalloc((void**)&h.h_fb_cnt, sizeof(int) * 4, hipHostMallocDefault);
+        if (e == hipSuccess && !h.fb_ev) e = hipEventCreateWithFlags(&h.fb_ev, hipEventDisableTiming);
+        if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid feedback buffers");
+        h.fb_cap = h.n_tiles;
+    }
+    h.fb_ok = false;
+    h.fb_cam_ok = false;
+    h.fb_hot_est = -1;
+    h.info_mode = -1;
+    h.state = 0;
+    return RT_OK;
+}
+
+// The measurement has landed in h_tr: the candidates (a refresh of a decided shape keeps them and the choice) and the
+// tile lists of every one of them, [hot tiles][cold 8x8 tiles] one after another (rtl::build_lists), staged to the device
+int hybrid_stage_lists(rt_ctx* ctx, const Launch& L) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    const rt_frame* f = L.f;
+    const int tx = L.A.tiles_x, ty = L.A.n_tiles / L.A.tiles_x;
+    std::vector<long long> dur(h.n_tiles);
+    for (size_t t = 0; t < h.n_tiles; t++) dur[t] = (long long)(h.h_tr[4 * t + 1] - h.h_tr[4 * t]);
+    std::vector<int> ord = centre_out(tx, ty);
+    if (!L.centre_out)
+        for (int t = 0; t < (int)ord.size(); t++) ord[t] = t;  // RT_DEAL_ROW_MAJOR
+    h.cold_regions = L.xcd_mode >= 1 && L.xcd_mode <= 3 && L.centre_out;
+    h.cold_mode = h.cold_regions ? L.xcd_mode : 0;
+    const bool keep = h.choice >= 0;  // a refresh: new lists, the same candidates and choice
+    if (!keep) h.nc = rtl::hybrid_candidates(L.caps, f->hot_pct, f->hot_kernel, h.cand);
+    const std::vector<int> lists =
+        rtl::build_lists(dur, tx, ty, f->width, f->n_rows, ord, h.cold_mode, h.cand, h.nc, h.cl);
+    if (!lists.empty()) {
+        // pinned staging: the last copy out of it ran before the measuring frame (stream order), which has
+        // finished; the device copy is stream-ordered after every frame that read the old lists
+        if (h.hl_cap < lists.size()) {
+            if (h.h_lists) (void)hipHostFree(h.h_lists);
+            h.h_lists = nullptr;
+            h.hl_cap = 0;
+            const hipError_t e = hipHostMalloc((void**)&h.h_lists, sizeof(int) * lists.size(), hipHostMallocDefault);
+            if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid lists");
+            h.hl_cap = lists.size();
+        }
+        if (h.lists_cap < lists.size()) {  // (rare: a new shape; hipFree waits for the device)
+            if (h.d_lists) (void)hipFree(h.d_lists);
+            h.d_lists = nullptr;
+            h.lists_cap = 0;
+            const hipError_t e = hipMalloc((void**)&h.d_lists, sizeof(int) * lists.size());
+            if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid lists");
+            h.lists_cap = lists.size();
+        }
+        std::memcpy(h.h_lists, lists.data(), sizeof(int) * lists.size());
+        const hipError_t e = hipMemcpyAsync(h.d_lists, h.h_lists, sizeof(int) * lists.size(), hipMemcpyHostToDevice,
+                                            ctx->stream);
+        if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid lists");
+    }
+    if (!keep) {
+        for (int c = 0; c < h.nc; c++)
+            for (int r = 0; r < rt_ctx::Hybrid::ROUNDS; r++) h.launch[c][r] = -1;
+        h.choice = h.nc == 1 ? 0 : -1;
+    }
+    h.frames = 0;
+    h.state = 2;
+    return RT_OK;
+}
+
+// The lists are ready: the chosen candidate; else the next trial; else, once the last trial has run, the choice
+int hybrid_choose(rt_ctx* ctx, Launch& L, Pick& pk) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    constexpr int R = rt_ctx::Hybrid::ROUNDS;
+    auto pick_of = [&](int c) { return h.cand[c].pct == 0 && !h.cand[c].lpt ? Pick{1, h.cand[c].cold} : Pick{2, c}; };
+    if (h.choice < 0) {
+        if (const int c = rtl::next_trial(&h.launch[0][0], h.nc, R, false, ctx->launches); c >= 0) {
+            pk = pick_of(c);
+            return RT_OK;
+        }
+        const long long last = rtl::latest_trial(&h.launch[0][0], h.nc, R);
+        bool done = false;
+        if (hipError_t e = in_flight(ctx->ev1s[last % rt_ctx::NEV], done); e != hipSuccess)
+            return fail(ctx, e, "rt_render: hybrid trials");
+        if (!done) return RT_OK;  // the trials are still running: the static rule's kernel
+        float t[rt_ctx::Hybrid::NCAND * R] = {};
+        for (int c = 0; c < h.nc; c++)
+            for (int r = rtl::HYBRID_WARM; r < R; r++) {
+                const int sl = (int)(h.launch[c][r] % rt_ctx::NEV);
+                const hipError_t e = hipEventElapsedTime(&t[c * R + r], ctx->ev0s[sl], ctx->ev1s[sl]);
+                if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid trials");
+            }
+        h.choice = rtl::hybrid_decide(t, h.nc, h.ms);
+        h.frames = 0;
+        if (tune_log()) {
+            std::fprintf(stderr, "[prt hybrid] %dx%d b%d:", L.f->width, L.f->n_rows, L.f->bounces);
+            for (int c = 0; c < h.nc; c++)
+                std::fprintf(stderr, " %s%d/coop%d/%s%s %.3f ms", h.cand[c].pct ? "hot>" : "whole", h.cand[c].pct,
+                             h.cand[c].lanes, variant_name(h.cand[c].cold), h.cand[c].lpt ? "/lpt" : "", h.ms[c]);
+            std::fprintf(stderr, " -> %d\n", h.choice);
+        }
+    }
+    L.li.settled = 1;
+    L.li.trial = 0;
+    pk = pick_of(h.choice);
+    return RT_OK;
+}
+
+// pk: what this frame of RT_VARIANT_HYBRID runs (the static rule's whole-frame kernel unless the state says otherwise)
+int hybrid_pick(rt_ctx* ctx, Launch& L, Pick& pk) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    const rtl::ShapeKey key = rtl::hybrid_key(ctx->scene_gen, *L.f);
+    const bool same = h.key == key;
+    pk = Pick{1, rtl::single_rule(L.caps)};
+    if (!h.ev) {
+        hipError_t e = hipEventCreateWithFlags(&h.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&h.fork, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&h.join, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h.s2, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail(ctx, e, "rt_render: hybrid events / stream");
+    }
+    // a decided shape's frames -- its periodic refresh (a measuring frame, li.refresh) and the frames while that
+    // measurement is in flight included -- are the rule's steady state (settled); a new shape's are trials
+    const bool decided = same && h.choice >= 0;
+    L.li.settled = decided ? 1 : 0;
+    L.li.trial = decided ? 0 : 1;
+    if (!same) {  // a new shape: measure it, once an earlier measurement in flight has landed in h_tr
+        if (h.state == 1) {
+            bool done = false;
+            if (hipError_t e = in_flight(h.ev, done); e != hipSuccess) return fail(ctx, e, "rt_render: hybrid measurement");
+            if (!done) return RT_OK;
+        }
+        if (int rc = hybrid_new_shape(ctx, key, (size_t)L.A.n_tiles)) return rc;
+    }
+    // renew a decided shape's lists with a measuring frame every REFRESH frames -- unless its frames feed their own
+    // tile times forward (PRT_FEEDBACK), which keeps the lists one frame old
+    if (!PRT_FEEDBACK && h.state == 2 && h.choice >= 0 && ++h.frames >= rt_ctx::Hybrid::REFRESH) h.state = 0;
+    if (h.state == 0) {
+        pk = Pick{0, 0};
+        return RT_OK;
+    }
+    if (h.state == 1) {
+        bool done = false;
+        if (hipError_t e = in_flight(h.ev, done); e != hipSuccess) return fail(ctx, e, "rt_render: hybrid measurement");
+        if (!done) {
+            if (h.choice >= 0 && h.cand[h.choice].pct == 0) pk.c = h.cand[h.choice].cold;
+            return RT_OK;
+        }
+        if (int rc = hybrid_stage_lists(ctx, L)) return rc;
+    }
+    return hybrid_choose(ctx, L, pk);
+}
+
+// The hot kernel's arguments of a hybrid launch: its own tiles (tiles_x wide, n_tiles of them in `order`, hottest
+// first), dealt from their own work counter
+rtd::KArgs hot_args(const rtd::KArgs& A, int tiles_x, int n_tiles, const int* order) {
+    rtd::KArgs B = A;
+    B.tiles_x = tiles_x;
+    B.n_tiles = n_tiles;
+    B.tile_order = order;
+    B.region_off = nullptr;
+    B.work = A.work + 224;
+    return B;
+}
+
+// One persistent grid of a hybrid launch
+struct Grid {
+    KFn k;
+    int blocks;  // 0: not launched
+    size_t dyn;
+    rtd::KArgs args;
+};
+// The two grids of a hybrid launch: the hot kernel on the context's second stream while the cold kernel runs on the
+// context stream, which waits for both; without a hot grid the cold kernel alone.
+int launch_hot_cold(rt_ctx* ctx, const Grid& hot, const Grid& cold) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    auto run = [](const Grid& g, hipStream_t s) {
+        if (g.blocks > 0) g.k<<<g.blocks, rtd::BLOCK, g.dyn, s>>>(g.args);
+    };
+    if (hot.blocks == 0) {
+        run(cold, ctx->stream);
+        HIPC(hipGetLastError());
+        return RT_OK;
+    }
+    HIPC(hipEventRecord(h.fork, ctx->stream));  // after the lists, the work / counter and the durations' resets
+    HIPC(hipStreamWaitEvent(h.s2, h.fork, 0));
+    run(hot, h.s2);
+    HIPC(hipGetLastError());
+    run(cold, ctx->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(h.join, h.s2));
+    HIPC(hipStreamWaitEvent(ctx->stream, h.join, 0));
+    return RT_OK;
+}
+
+// RT_VARIANT_HYBRID, one frame: the hot tiles (ctx->hy lists) through k_coop on the context's second stream
+// while the cold kernel (k_persist, or the shadow pool) renders the cold 8x8 tiles on the context stream; both
+// persistent grids together fill the chip (rtl::hybrid_grids).
+int launch_hybrid(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    const int n_hot = h.cl[c].n_hot, n_cold = h.cl[c].n_cold;
+    int* lists = h.d_lists + h.cl[c].at;
+    const int g = h.cand[c].lanes;
+    const KFn kc = coop_kernel(A.bounces, g, count);
+    int tw, th;
+    hot_tile(g, tw, th);
+    const rtd::KArgs B = hot_args(A, (A.W + tw - 1) / tw, n_hot, lists);
+    rtd::KArgs P = A;
+    P.n_tiles = n_cold;
+    P.region_off = h.cold_regions ? lists + n_hot : nullptr;
+    P.tile_order = lists + n_hot + (h.cold_regions ? 9 : 0);
+    size_t dyn = 0;
+    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
+    const int rp = resident(kp, ctx->device, 8, dyn);
+    const int rcp = resident(kc, ctx->device);
+    int nc, np;
+    rtl::hybrid_grids(rp, rcp, n_hot, n_cold, nc, np);
+    // (no hot tiles: a whole frame in the measured order)
+    return launch_hot_cold(ctx, Grid{kc, nc, 0, B}, Grid{kp, n_cold > 0 ? np : 0, dyn, with_slots(P, dyn)});
+}
+
+// A decided shape's frame under the per-frame feedback (rt_feedback.hpp): candidate c's lists built on the device from
+// the previous frame's tile durations (k_fb_max, k_fb_count, k_fb_place), the durations cleared, then c's kernels as launch_hybrid launches
+// them, every one reading its list and count from the device and recording this frame's durations. The grids are sized
+// by a recent frame's hot count, read back without a wait.
+int launch_hybrid_fb(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    const int g = h.cand[c].lanes == 2 ? 2 : 4;
+    const bool hot = h.cand[c].pct > 0;
+    int tw, th;
+    hot_tile(g, tw, th);
+    const int ctw = (A.W + tw - 1) / tw, cth = (A.n_rows + th - 1) / th;
+    int* d_hot = h.d_fb;
+    int* d_cold = h.d_fb + 4 * h.n_tiles;
+    int* d_cnt = d_cold + 9 + h.n_tiles;
+    const int tx = A.tiles_x, ty = A.n_tiles / A.tiles_x;
+    if (h.info_mode != h.cold_mode) {  // the shape's per-tile region and hot-kernel tile counts, once
+        std::vector<unsigned char> info(h.n_tiles);
+        for (int t = 0; t < A.n_tiles; t++) info[t] = rtd::fb_tile_info(t, tx, ty, h.cold_mode, A.W, A.n_rows);
+        HIPC(hipMemcpy(h.d_info, info.data(), info.size(), hipMemcpyHostToDevice));
+        h.info_mode = h.cold_mode;
+    }
+    // (hot set: at most half the 8x8 tiles, as the host's lists, counted in hot-kernel tiles)
+    // (d_cost holds n_tiles + 1 words: A.n_tiles is this shape's n_tiles, the maximum's word right after the tiles)
+    // the last frame's times in, this frame's buffer cleared by k_fb_max (with the frame's counters and work words)
+    unsigned* const cost_in = h.cost_at(h.cost_cur);
+    unsigned* const cost_out = h.cost_at(h.cost_cur ^ 1);
+    rtd::FbArgs F{cost_in, A.n_tiles, tx, ty, h.cand[c].pct, (int)(h.n_tiles / 2) * (8 / tw) * (8 / th), tw, th, ctw, cth, h.cold_mode,
+                  h.d_info, d_hot, d_cold, d_cnt, (unsigned*)(d_cnt + 4), (unsigned*)(d_cnt + 4) + rtd::FB_G * rtd::FB_TK, 0,
+                  cost_out,
+                  ctx->batch_sum ? nullptr : ctx->d_counters, rtd::NCOUNT, ctx->d_work, 1024 / 4};
+    {  // the camera against the last feedback frame's (rt_feedback.hpp FbArgs::moved)
+        float cam[12];
+        std::memcpy(cam, A.pos, sizeof(float) * 3);
+        std::memcpy(cam + 3, A.ul, sizeof(float) * 3);
+        std::memcpy(cam + 6, A.ix, sizeof(float) * 3);
+        std::memcpy(cam + 9, A.iy, sizeof(float) * 3);
+        F.moved = h.fb_cam_ok && std::memcmp(cam, h.fb_cam, sizeof cam) != 0;
+        std::memcpy(h.fb_cam, cam, sizeof cam);
+        h.fb_cam_ok = true;
+    }
+    rtd::k_fb_max<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
+    rtd::k_fb_count<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
+    rtd::k_fb_place<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
+    HIPC(hipGetLastError());
+    h.cost_cur ^= 1;
+    if (h.fb_pending) {  // a recent frame's hot count (grid size), if its copy has landed: a query, never a wait
+        const hipError_t q = hipEventQuery(h.fb_ev);
+        if (q == hipSuccess) {
+            h.fb_hot_est = h.h_fb_cnt[0];
+            h.fb_est_c = h.fb_pend_c;
+            h.fb_pending = false;
+        } else if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+        } else {
+            return fail(ctx, q, "rt_render: hybrid feedback count");
+        }
+    }
+    if (hot && !h.fb_pending) {
+        HIPC(hipMemcpyAsync(h.h_fb_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipEventRecord(h.fb_ev, ctx->stream));
+        h.fb_pending = true;
+        h.fb_pend_c = c;
+    }
+    const KFn kc = coop_kernel(A.bounces, g, count);
+    // the hot kernel's tiles, hottest first, their number on the device
+    rtd::KArgs B = hot_args(A, ctw, 4 * (int)h.n_tiles, d_hot);
+    B.n_tiles_dev = d_cnt;
+    B.tile_cost = cost_out;
+    rtd::KArgs P = A;  // the cold 8x8 tiles by region, costliest first (the region offsets hold their number)
+    P.region_off = d_cold;
+    P.tile_order = d_cold + 9;
+    P.tile_cost = cost_out;
+    size_t dyn = 0;
+    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
+    if (build) *build |= RT_BUILD_FEEDBACK;
+    const int rp = resident(kp, ctx->device, 8, dyn);
+    const int rcp = resident(kc, ctx->device);
+    const int est = h.fb_hot_est >= 0 && h.fb_est_c == c ? h.fb_hot_est : h.cl[c].n_hot;  // (another candidate's: its own)
+    // the hot kernel's grid from a count a few frames old: with headroom (2x + 64 tiles), since a hot set that grew
+    // past its grid's waves -- a moving camera's, after frames of few hot tiles -- is rendered by too few waves (dragon
+    // walkthrough frames of 3-6 ms among ~1.1 ms ones); a persistent grid's waves that find no tile exit at once
+    const int est_h = 2 * est + 64;
+    int nc, np;
+    rtl::hybrid_grids(rp, rcp, hot ? est_h : 0, A.n_tiles, nc, np);
+    // (no hot candidate: the whole frame, costliest first)
+    return launch_hot_cold(ctx, Grid{kc, nc, 0, B}, Grid{kp, np, dyn, with_slots(P, dyn)});
+}
+
+// the persistent grids' work counters (d_work), and the ray counters, which restart with every launch (rt_get_stats
+// reports the frame, not the trial launches)
+int clear_counters(rt_ctx* ctx) {
+    if (!ctx->batch_sum)  // a per-frame loop of a batch keeps adding to the batch's counters
+        HIPC(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * rtd::NCOUNT, ctx->stream));
+    HIPC(hipMemsetAsync(ctx->d_work, 0, 1024, ctx->stream));
+    return RT_OK;
+}
+
+// One frame of RT_VARIANT_HYBRID: what hybrid_pick says (P: the whole frame's arguments in the launch's dealing order)
+int dispatch_hybrid(rt_ctx* ctx, Launch& L, int cp, rtd::KArgs& P) {
+    rt_ctx::Hybrid& h = ctx->hy;
+    rt_launch_info& li = L.li;
+    Pick pk{};
+    if (int rc = hybrid_pick(ctx, L, pk)) return rc;
+    // (a hybrid frame on device-built lists has its list builder clear the counters)
+    const bool fb = PRT_FEEDBACK && pk.kind == 2 && h.fb_ok && h.d_cost;
+    if (PRT_FEEDBACK && !fb)
+        if (int rc = clear_counters(ctx)) return rc;
+    // the frame's HIP-event time starts here, after the host work of the pick (the trials compare them)
+    HIPC(hipEventRecord(ctx->ev0, ctx->stream));
+    if (pk.kind == 2) {
+        li.hot_pct = h.cand[pk.c].pct;
+        li.hot_lanes = h.cand[pk.c].lanes;
+        li.cold_variant = h.cand[pk.c].cold;
+    }
+    // every frame of the shape records its tiles' durations (rt_feedback.hpp); a hybrid candidate's frame --
+    // tried or chosen -- builds its lists from the previous frame's first, on the device (the memset follows
+    // that build: k_coop's hot tiles combine their group tiles' times by atomic max). The trials too: with a
+    // moving camera the measuring frame's lists age frame by frame, and a candidate tried later would be
+    // priced with older lists than one tried first (a car_boxed walkthrough settled on the wrong candidate).
+    if (PRT_FEEDBACK && h.d_cost) {
+        if (fb) {
+            const int rc = launch_hybrid_fb(ctx, L.A, L.count, pk.c, &li.build);
+            h.fb_ok = rc == RT_OK;
+            return rc;
+        }
+        unsigned* w = h.cost_at(h.cost_cur ^ 1);
+        HIPC(hipMemsetAsync(w, 0, sizeof(unsigned) * (h.n_tiles + 1), ctx->stream));
+        P.tile_cost = w;
+        L.A.tile_cost = w;
+        h.cost_cur ^= 1;
+        h.fb_ok = true;  // (this frame, in stream order, fills it)
+    }
+    if (pk.kind == 2) return launch_hybrid(ctx, L.A, L.count, pk.c, &li.build);
+    if (pk.kind == 0) {  // measuring frame: k_persist with per-tile times, copied to the host behind it
+        li.variant = RT_VARIANT_PERSIST;
+        li.refresh = h.choice >= 0 ? 1 : 0;  // a decided shape's periodic list refresh (settled)
+        li.trial = li.refresh ? 0 : 1;
+        li.settled = li.refresh;
+        P.tile_trace = h.d_tr;
+        launch_paths(P, RT_VARIANT_PERSIST, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(h.h_tr, h.d_tr, sizeof(unsigned long long) * 4 * h.n_tiles, hipMemcpyDeviceToHost,
+                            ctx->stream));
+        HIPC(hipEventRecord(h.ev, ctx->stream));
+        h.state = 1;
+        return RT_OK;
+    }
+    // a whole-frame kernel: chosen, tried, or while the measurement / trials are on their way
+    li.variant = pk.c;
+    launch_paths(P, pk.c, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
+    return RT_OK;
+}
+
+// one frame (or one batch) of configuration (variant md, cap cp)
+int dispatch(rt_ctx* ctx, Launch& L, int md, int cp) {
+    const rt_frame* f = L.f;
+    // (a hybrid frame clears after its pick: dispatch_hybrid)
+    if (!(PRT_FEEDBACK && md == RT_VARIANT_HYBRID))
+        if (int rc = clear_counters(ctx)) return rc;
+    L.li.variant = md;
+    if (L.kernel == RT_KERNEL_STRICT) {
+        L.li.variant = 0;
+        const dim3 grid((f->width + 15) / 16, (f->n_rows + 15) / 16);
+        tiles_kernel(f->bounces, L.count)<<<grid, rtd::BLOCK, 0, ctx->stream>>>(L.A);
+        return RT_OK;
+    }
+    if (md == RT_VARIANT_COOP2 || md == RT_VARIANT_COOP4) {
+        rtd::KArgs B = L.A;
+        const int gr = md == RT_VARIANT_COOP2 ? 2 : 4;
+        int tw, th;
+        hot_tile(gr, tw, th);  // rtd::GTile<gr>
+        B.tiles_x = (f->width + tw - 1) / tw;
+        const int ty = (f->n_rows + th - 1) / th;
+        B.n_tiles = B.tiles_x * ty;
+        if (int rc = order_for(ctx, L, B.tiles_x, ty, B.tile_order)) return rc;
+        return launch_group(B, gr, L.count, ctx->device, ctx->stream, cp);
+    }
+    rtd::KArgs P = L.A;
+    if (L.region_off) {
+        P.region_off = L.region_off;
+        P.tile_order = L.region_order;
+    }
+    if (md == RT_VARIANT_HYBRID) return dispatch_hybrid(ctx, L, cp, P);
+    launch_paths(P, md, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &L.li.build);
+    return RT_OK;
+}
+
+// diagnostics: PRT_TILE_TRACE=<file> writes 4 x uint64 per tile of a k_persist frame (rt_kernels.hpp)
+// (s_memrealtime, 100 MHz); synchronous, never used by tests or the bench
+int write_tile_trace(rt_ctx* ctx, unsigned long long* d_trace, size_t n_tiles, const char* path) {
+    std::vector<unsigned long long> h(4 * n_tiles);
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMemcpy(h.data(), d_trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    HIPC(hipFree(d_trace));
+    if (FILE* fp = std::fopen(path, "wb")) {
+        std::fwrite(h.data(), sizeof(unsigned long long), h.size(), fp);
+        std::fclose(fp);
+    }
+    return RT_OK;
+}
+
+// rt_render / rt_render_frames: n_frames frames of the same shape (cameras cams[0..n_frames-1]); outputs
+// [n_frames][n_rows][width]... Persistent fast configurations trace the whole batch in ONE launch (frames'
+// tiles interleaved in the dealing order); other kernels launch once per frame.
+int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_frame* f, const rt_outputs* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_render: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!cams || !f) return arg_err(ctx, "rt_render: null camera/frame");
+    int spp_grid = 1;
+    if (const char* why = rtl::check_frame(*f, n_frames, spp_grid)) return arg_err(ctx, why);
+    HIPC(hipSetDevice(ctx->device));
+    Launch L;
+    L.f = f;
+    L.cams = cams;
+    L.n_frames = n_frames;
+    L.kernel = f->kernel == RT_KERNEL_AUTO ? RT_KERNEL_FAST : f->kernel;
+    L.count = (ctx->flags & RT_FLAG_COUNTERS) != 0;
+    rtd::KArgs& A = L.A;
+    const size_t pixels = (size_t)f->width * f->n_rows;  // per frame
+    const size_t all_px = pixels * (size_t)n_frames;
+    float* rgb = out ? out->rgb : nullptr;
+    unsigned* bgra = out ? out->bgra : nullptr;
+    if (!rgb && !bgra)
+        if (int rc = own_rgb(ctx, all_px, rgb)) return rc;
+    fill_args(ctx, L, out, rgb, bgra, spp_grid);
+    if (n_frames > 1 && L.kernel != RT_KERNEL_FAST) {  // one launch per frame, outputs at frame offsets
         for (int i = 0; i < n_frames; i++) {
             rt_outputs o{rgb ? rgb + 3 * pixels * i : nullptr, A.hit ? A.hit + pixels * i : nullptr,
                          A.t ? A.t + pixels * i : nullptr,
@@ -1409,570 +1916,43 @@ int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_fram
     }
     A.n_frames = n_frames;
     A.frame_px = pixels;
-    if (kernel == RT_KERNEL_FAST && (!ctx->d_pathbuf || !ctx->d_gstack || !ctx->d_lanebuf)) {
-        // (each buffer its own check: a failed allocation of one of them leaves the others, and the next render
-        // retries the missing one instead of launching with a null buffer)
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        const size_t waves = (size_t)cus * 8 * (rtd::BLOCK / 64);  // <= 8 workgroups per CU (resident() cap)
-        // path buffer of the PB kernels: every resident wave, MAXB <= 8 levels
-        if (!ctx->d_pathbuf) HIPC(hipMalloc((void**)&ctx->d_pathbuf, sizeof(float4) * waves * 8 * 64));
-        // DYN kernels' binary-walk stacks: STACK ints per lane of every resident workgroup (<= 8 per CU)
-        if (!ctx->d_gstack) HIPC(hipMalloc((void**)&ctx->d_gstack, sizeof(int) * (size_t)cus * 8 * rtd::STACK * rtd::BLOCK));
-        // the multi-sample builds' per-lane slots (the running sum and the pixel between samples): every resident lane
-        if (!ctx->d_lanebuf) HIPC(hipMalloc((void**)&ctx->d_lanebuf, sizeof(float4) * (size_t)cus * 8 * rtd::BLOCK));
-    }
+    if (L.kernel == RT_KERNEL_FAST)
+        if (int rc = walk_buffers(ctx)) return rc;
     A.pathbuf = ctx->d_pathbuf;
     A.lanebuf = ctx->d_lanebuf;
     A.gstack = ctx->d_gstack;
-    A.wcap = ctx->wide_n > 0 ? std::max(1, std::max(ctx->wide_depth, std::max(ctx->unit_depth, ctx->prim_depth))) : 0;
+    A.wcap = ctx->wide.n > 0 ? std::max(1, std::max(ctx->wide.depth, std::max(ctx->unit.depth, ctx->prim.depth))) : 0;
     if (n_frames > 1) {  // the batch's cameras, uploaded when they change
         if (int rc = upload_cams(ctx, cams, n_frames)) return rc;
         A.cams = ctx->d_cams;
     }
     A.regroup = f->regroup > 0 ? f->regroup : 16;
-    const bool count = (ctx->flags & RT_FLAG_COUNTERS) != 0;
-    dim3 grid((f->width + 15) / 16, (f->n_rows + 15) / 16);
     const int slot = (int)(ctx->launches % rt_ctx::NEV);
     ctx->ev0 = ctx->ev0s[slot];
     ctx->ev1 = ctx->ev1s[slot];
-    // diagnostics: PRT_TILE_TRACE=<file> writes 4 x uint64 per tile of a k_persist frame (rt_kernels.hpp)
-    // (s_memrealtime, 100 MHz); synchronous, never used by tests or the bench
-    const char* trace_path = std::getenv("PRT_TILE_TRACE");
+    const char* trace_path = std::getenv("PRT_TILE_TRACE");  // (write_tile_trace)
     unsigned long long* d_trace = nullptr;
     const size_t trace_n = (size_t)A.n_tiles;
-    if (trace_path && kernel == RT_KERNEL_FAST && n_frames == 1 && f->spp == 1) {
+    if (trace_path && L.kernel == RT_KERNEL_FAST && n_frames == 1 && f->spp == 1) {
         HIPC(hipMalloc((void**)&d_trace, sizeof(unsigned long long) * 4 * trace_n));
         HIPC(hipMemsetAsync(d_trace, 0, sizeof(unsigned long long) * 4 * trace_n, ctx->stream));
         A.tile_trace = d_trace;
     }
-    // Tile dealing order of the persistent kernels: centre-out (default). The frame ends when the slowest
-    // tile does (PRT_TILE_TRACE: 8x8 tiles range from 2 us to ~1.9 ms; expensive ones are deep reflection
-    // chains, usually on the object in view); dealing from the centre starts them first (bench frame
-    // -7 %). RT_DEAL_ROW_MAJOR: row-major. One cached permutation per tile grid.
-    const bool dealt_centre_out = kernel == RT_KERNEL_FAST && f->dealing != RT_DEAL_ROW_MAJOR;
-    auto order_for = [&](int tx, int ty, const int*& out_ord) -> int {
-        out_ord = nullptr;
-        if (!dealt_centre_out) return RT_OK;
-        const long long key = ((long long)tx << 32) | (unsigned)ty;
-        auto it = ctx->orders.find(key);
-        if (it != ctx->orders.end()) {
-            out_ord = it->second;
-            return RT_OK;
-        }
-        const std::vector<int> ord = centre_out(tx, ty);
-        int* d = nullptr;
-        HIPC(hipMalloc((void**)&d, sizeof(int) * ord.size()));
-        HIPC(hipMemcpy(d, ord.data(), sizeof(int) * ord.size(), hipMemcpyHostToDevice));
-        ctx->orders[key] = d;
-        out_ord = d;
-        return RT_OK;
-    };
-    if (int rc = order_for(A.tiles_x, A.n_tiles / A.tiles_x, A.tile_order)) return rc;
-    // XCD-aware dealing of k_persist: the centre-out order split into 8 spatial regions, region r drained first by
-    // the workgroups on XCD r (rtd::next_item), so each XCD's L2 holds the part of the scene its region's rays
-    // touch. rt_frame.dealing: BLOCKS = 4 x 2 blocks of tiles, ROWS = 8 bands of tile rows, COLUMNS = 8 bands of
-    // tile columns, GLOBAL = one counter. Same-box, ms per frame: 16-frame batches of the full frame, dragon 1.060
-    // (global) / 0.938 (blocks) / 0.980 (rows) / 0.942 (columns), sportscar 0.599 / 0.504, car_boxed 1.067 / 1.041;
-    // a single frame 1.862 / 1.871 (blocks) / 1.732 (rows); an 8-GPU rank's rows, batched, 0.220 / 0.208 (blocks) /
-    // 0.202 (rows). Default: blocks for batches of the full frame, row bands otherwise. Device layout: 9 region
-    // offsets, then the concatenated regions' tiles.
-    const int* region_off = nullptr;
-    const int* region_order = nullptr;
-    const bool full_frame = f->row_offset == 0 && f->n_rows == f->height;
-    const int xcd_mode = f->dealing == RT_DEAL_DEFAULT ? (n_frames > 1 && full_frame ? 3 : 1)
-                         : f->dealing == RT_DEAL_ROWS    ? 1
-                         : f->dealing == RT_DEAL_COLUMNS ? 2
-                         : f->dealing == RT_DEAL_BLOCKS  ? 3
-                                                         : 0;
-    auto regions_for = [&](int tx, int ty, const int*& roff, const int*& rord) -> int {
-        roff = rord = nullptr;
-        if (!(dealt_centre_out && xcd_mode >= 1 && xcd_mode <= 3)) return RT_OK;
-        const long long key = ((long long)xcd_mode << 58) | ((long long)tx << 32) | (unsigned)ty;
-        auto it = ctx->orders.find(key);
-        if (it == ctx->orders.end()) {
-            const std::vector<int> dev = region_layout(centre_out(tx, ty), tx, ty, xcd_mode);
-            int* d = nullptr;
-            HIPC(hipMalloc((void**)&d, sizeof(int) * dev.size()));
-            HIPC(hipMemcpy(d, dev.data(), sizeof(int) * dev.size(), hipMemcpyHostToDevice));
-            it = ctx->orders.emplace(key, d).first;
-        }
-        roff = it->second;
-        rord = it->second + 9;
-        return RT_OK;
-    };
-    if (int rc = regions_for(A.tiles_x, A.n_tiles / A.tiles_x, region_off, region_order)) return rc;
-    // RT_KERNEL_FAST launch configurations (rt_frame.variant; every one renders the same bits):
-    //   PERSIST / PERSIST4  k_persist, one lane per pixel path, walks in lockstep, 8x8 tiles;
-    //   SHPOOL              k_persist at 4 waves with each level's shadow rays walked as a per-wave pool;
-    //   COOP2/4             k_coop (rt_coop.hpp): G lanes per ray, 64/G-pixel tiles — shorter chains per tile,
-    //                       which is what a frame split over many GPUs (few tiles per wave) is bound by;
-    //   HYBRID              single frames: the costliest tiles through k_coop on a second stream (§3e).
-    const bool wide_ok = kernel == RT_KERNEL_FAST && ctx->wide_n > 0;
-    // the shadow pool: 1..32 lights (a 32-bit visibility word per pixel) and the LDS path buffer at 4 workgroups per CU
-    const bool shp_ok = wide_ok && ctx->n_lights >= 1 && ctx->n_lights <= 32 && ctx->pk_ok && ctx->tq_ok &&
-                        (f->bounces <= 4 ? pbl_fits<4>(A, ctx->device, 1) : pbl_fits<8>(A, ctx->device, 1));
-    const bool shd_ok = shp_ok && ctx->n_lights <= 8 && (f->bounces <= 4 ? pbl_fits<4>(A, ctx->device, 2) : pbl_fits<8>(A, ctx->device, 2));
-    auto usable = [&](int v) {
-        if (A.tile_trace) return v == RT_VARIANT_PERSIST;  // (diagnostics: the 3-wave kernel's tile trace)
-        if (v == RT_VARIANT_COOP2 || v == RT_VARIANT_COOP4) return wide_ok;
-        if (v == RT_VARIANT_SHPOOL) return shp_ok;
-        if (v == RT_VARIANT_SHDEFER) return shd_ok;
-        if (v == RT_VARIANT_HYBRID) return wide_ok && n_frames == 1 && fs == 0 && f->spp == 1;
-        return true;
-    };
-    // The default rule (measured): frame batches and spp > 1 fill the chip, so the kernel with the best
-    // throughput — the shadow pool for scenes of 2+ lights whose LDS path buffer fits (dragon 0.708 -> 0.666 ms per
-    // frame in 20-frame batches; one light leaves nothing to pool: car_boxed 0.868 vs 0.902), else k_persist at 4
-    // waves; a single 1-spp frame is tail-bound: the hybrid launch, which measures its candidates on the frames of
-    // the shape and keeps the fastest (k_persist where it cannot run).
-    const bool pool_rule = shp_ok && ctx->n_lights >= 2;
-    // the pool kernel of the rules: one pool for all levels where its larger LDS path buffer fits (dragon 20-frame
-    // batches 0.655 -> 0.639 ms per frame, single frames 1.145 -> 1.091 ms; SIMD efficiency 0.59 -> 0.68), else one
-    // per level
-    const int pool_v = shd_ok ? RT_VARIANT_SHDEFER : RT_VARIANT_SHPOOL;
-    int mode = f->variant;
-    if (mode == RT_VARIANT_DEFAULT)
-        mode = (n_frames > 1 || f->spp > 1) ? (pool_rule ? pool_v : RT_VARIANT_PERSIST4) : RT_VARIANT_HYBRID;
-    if ((mode == RT_VARIANT_SHPOOL && !shp_ok) || (mode == RT_VARIANT_SHDEFER && !shd_ok))
-        mode = RT_VARIANT_PERSIST4;  // (no room for the pool: PERSIST4 itself)
-    if (!usable(mode)) mode = RT_VARIANT_PERSIST;  // (no wide view, or a diagnostics trace)
-    // the whole-frame kernel of a single frame while the hybrid launch measures or tries its candidates
-    const int single_rule = pool_rule ? pool_v : RT_VARIANT_PERSIST;
-    const int cap = f->waves_cap;
-    rt_launch_info li{};  // what this render runs (rt_get_launch_info)
-    li.settled = 1;
-    // The default rule for frame batches and spp > 1 where the shadow pool can run: measured, not guessed. Whether the
-    // pool pays depends on the scene (dragon 20-frame batches 0.708 -> 0.666 ms per frame; two_cars 4K 1.881 vs 1.917,
-    // car_boxed 0.868 vs 0.902), so the first launches of a shape try PERSIST4 and SHPOOL ROUNDS times each (their own
-    // HIP events, read by a query once the last has run) and the faster per frame renders from then on. A context with
-    // traversal counters never tries (the counters of a trial would be another kernel's): it keeps the static rule.
-    if (f->variant == RT_VARIANT_DEFAULT && kernel == RT_KERNEL_FAST && !A.tile_trace && !count &&
-        (n_frames > 1 || f->spp > 1) && shp_ok) {
-        rt_ctx::BatchRule* br = nullptr;
-        for (auto& b : ctx->brules)
-            if (b.scene == ctx->scene_gen && b.W == f->width && b.rows == f->n_rows && b.off == f->row_offset &&
-                b.stride == f->row_stride && b.block == rb && b.shift == fs && b.bounces == f->bounces &&
-                b.spp == f->spp && b.frames == n_frames && b.dealing == f->dealing && b.cap_req == f->waves_cap)
-                br = &b;
-        if (!br) {
-            if (ctx->brules.size() >= 16) ctx->brules.erase(ctx->brules.begin());
-            ctx->brules.emplace_back();
-            br = &ctx->brules.back();
-            *br = rt_ctx::BatchRule{ctx->scene_gen, f->width, f->n_rows, f->row_offset, f->row_stride, rb, fs,
-                                     f->bounces, f->spp, n_frames, f->dealing, f->waves_cap};
-        }
-        rt_ctx::BatchRule& b = *br;
-        const int cand[2] = {RT_VARIANT_PERSIST4, pool_v};
-        const int nc = 2;
-        int pick = -1;
-        if (b.choice < 0) {
-            for (int r = 0; r < rt_ctx::BatchRule::ROUNDS && pick < 0; r++)
-                for (int c = 0; c < nc && pick < 0; c++)
-                    if (b.launch[c][r] < 0 || ctx->launches - b.launch[c][r] >= rt_ctx::NEV) {  // untried (or events reused)
-                        b.launch[c][r] = ctx->launches;
-                        pick = c;
-                    }
-            if (pick < 0) {  // every trial enqueued: decide once the last has run (a query, never a wait)
-                long long last = 0;
-                for (int c = 0; c < nc; c++)
-                    for (long long x : b.launch[c]) last = std::max(last, x);
-                const hipError_t q = hipEventQuery(ctx->ev1s[last % rt_ctx::NEV]);
-                if (q == hipSuccess) {
-                    float ms[2] = {1e30f, 1e30f};
-                    constexpr int R = rt_ctx::BatchRule::ROUNDS;
-                    float t[2][R];
-                    float med_max = 0.0f;
-                    for (int c = 0; c < nc; c++) {
-                        for (int r = 0; r < R; r++) {
-                            const int sl = (int)(b.launch[c][r] % rt_ctx::NEV);
-                            HIPC(hipEventElapsedTime(&t[c][r], ctx->ev0s[sl], ctx->ev1s[sl]));
-                        }
-                        std::sort(t[c], t[c] + R);
-                        med_max = std::max(med_max, t[c][R / 2]);
-                    }
-                    // one statistic for every candidate (like with like): the median when the launches are long
-                    // (some candidate's median over LONG_MS), else the minimum
-                    const bool by_median = med_max > rt_ctx::BatchRule::LONG_MS;
-                    for (int c = 0; c < nc; c++) ms[c] = by_median ? t[c][R / 2] : t[c][0];
-                    b.choice = 0;
-                    for (int c = 1; c < nc; c++)
-                        if (ms[c] < ms[b.choice]) b.choice = c;
-                    if (const char* l = std::getenv("PRT_TUNE_LOG"); l && std::atoi(l) == 1)
-                        std::fprintf(stderr, "[prt batch] %dx%d f%d spp%d: persist4 %.3f ms, %s %.3f ms -> %s\n",
-                                     f->width, f->n_rows, n_frames, f->spp, ms[0], variant_name(cand[1]), ms[1],
-                                     variant_name(cand[b.choice]));
-                } else if (q != hipErrorNotReady) {
-                    return fail(ctx, q, "rt_render: batch rule trials");
-                } else {
-                    (void)hipGetLastError();  // not an error: the trials are still running
-                }
-            }
-        }
-        if (b.choice >= 0) {
-            mode = cand[b.choice];
-        } else {
-            mode = pick >= 0 ? cand[pick] : (pool_rule ? pool_v : RT_VARIANT_PERSIST4);
-            li.trial = 1;
-            li.settled = 0;
-        }
-    }
-    // RT_VARIANT_HYBRID: what this single frame runs. The state is keyed by the frame's SHAPE, not its camera (a
-    // walkthrough moves it every frame). The first frame of a shape measures: k_persist with per-tile times, copied to
-    // pinned host memory behind it. Once they have arrived (an event query, never a wait) the tile lists of every
-    // candidate are built and copied in stream order, and the next frames try the candidates ROUNDS times each,
-    // timed by their own HIP events; when the last trial has finished (a query) the fastest minimum renders from then
-    // on (PRT_TUNE_LOG=1 prints them). Every REFRESH frames of the shape a measuring frame renews the tile lists for
-    // a moving camera (the choice stays). While a measurement or the trials are in flight, a frame runs the static
-    // rule's whole-frame kernel. rt_frame.hot_pct > 0 fixes the threshold (no trials).
-    // kind 0: measuring frame; 1: whole-frame variant c; 2: hybrid candidate c's launch (lists at ctx->hy)
-    struct Pick {
-        int kind, c;
-    };
-    auto hybrid_pick = [&](int& rc) -> Pick {
-        rt_ctx::Hybrid& h = ctx->hy;
-        const bool same = h.scene == ctx->scene_gen && h.W == f->width && h.rows == f->n_rows && h.off == f->row_offset &&
-                          h.stride == f->row_stride && h.block == rb && h.bounces == f->bounces &&
-                          h.dealing == f->dealing && h.pct_req == f->hot_pct && h.hk_req == f->hot_kernel;
-        auto err = [&](hipError_t e, const char* what) { rc = fail(ctx, e, what); return Pick{1, single_rule}; };
-        auto in_flight = [&](hipEvent_t e, bool& done) -> hipError_t {  // query, never wait
-            const hipError_t q = hipEventQuery(e);
-            done = q == hipSuccess;
-            if (q == hipErrorNotReady) {
-                (void)hipGetLastError();  // not an error: still running
-                return hipSuccess;
-            }
-            return q;
-        };
-        if (!h.ev) {
-            hipError_t e = hipEventCreateWithFlags(&h.ev, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h.fork, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h.join, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&h.s2, hipStreamNonBlocking);
-            if (e != hipSuccess) return err(e, "rt_render: hybrid events / stream");
-        }
-        // a decided shape's frames -- its periodic refresh (a measuring frame, li.refresh) and the frames while that
-        // measurement is in flight included -- are the rule's steady state (settled); a new shape's are trials
-        const bool decided = same && h.choice >= 0;
-        li.settled = decided ? 1 : 0;
-        li.trial = decided ? 0 : 1;
-        if (!same) {  // a new shape: measure it, once an earlier measurement in flight has landed in h_tr
-            if (h.state == 1) {
-                bool done = false;
-                if (hipError_t e = in_flight(h.ev, done); e != hipSuccess) return err(e, "rt_render: hybrid measurement");
-                if (!done) return Pick{1, single_rule};
-            }
-            h.scene = ctx->scene_gen;
-            h.W = f->width;
-            h.rows = f->n_rows;
-            h.off = f->row_offset;
-            h.stride = f->row_stride;
-            h.block = rb;
-            h.bounces = f->bounces;
-            h.dealing = f->dealing;
-            h.pct_req = f->hot_pct;
-            h.hk_req = f->hot_kernel;
-            h.choice = -1;
-            h.n_tiles = (size_t)A.n_tiles;
-            if (h.tr_cap < h.n_tiles) {  // (no measurement in flight writes h_tr now)
-                if (h.d_tr) (void)hipFree(h.d_tr);
-                if (h.h_tr) (void)hipHostFree(h.h_tr);
-                h.d_tr = h.h_tr = nullptr;
-                h.tr_cap = 0;
-                hipError_t e = hipMalloc((void**)&h.d_tr, sizeof(unsigned long long) * 4 * h.n_tiles);
-                if (e == hipSuccess) e = hipHostMalloc((void**)&h.h_tr, sizeof(unsigned long long) * 4 * h.n_tiles,
-                                                       hipHostMallocDefault);
-                if (e != hipSuccess) return err(e, "rt_render: hybrid tile times");
-                h.tr_cap = h.n_tiles;
-            }
-            if (h.fb_cap < h.n_tiles) {  // the feedback's buffers (rt_feedback.hpp); no frame of the old shape runs now
-                if (h.fb_pending) (void)hipEventSynchronize(h.fb_ev);
-                if (h.d_cost) (void)hipFree(h.d_cost);
-                if (h.d_fb) (void)hipFree(h.d_fb);
-                if (h.d_info) (void)hipFree(h.d_info);
-                h.d_cost = nullptr;
-                h.d_fb = nullptr;
-                h.d_info = nullptr;
-                h.fb_cap = 0;
-                hipError_t e = hipMalloc((void**)&h.d_cost, sizeof(unsigned) * 2 * (h.n_tiles + 1));
-                if (e == hipSuccess) e = hipMalloc((void**)&h.d_fb, sizeof(int) * (5 * h.n_tiles + 13 + rtd::FB_G * (rtd::FB_TK + 3)));
-                if (e == hipSuccess) e = hipMalloc((void**)&h.d_info, h.n_tiles);
-                if (e == hipSuccess && !h.h_fb_cnt) e = hipHostMalloc((void**)&h.h_fb_cnt, sizeof(int) * 4, hipHostMallocDefault);
-                if (e == hipSuccess && !h.fb_ev) e = hipEventCreateWithFlags(&h.fb_ev, hipEventDisableTiming);
-                if (e != hipSuccess) return err(e, "rt_render: hybrid feedback buffers");
-                h.fb_cap = h.n_tiles;
-            }
-            h.fb_ok = false;
-            h.fb_cam_ok = false;
-            h.fb_hot_est = -1;
-            h.info_mode = -1;
-            h.state = 0;
-        }
-        // renew a decided shape's lists with a measuring frame every REFRESH frames -- unless its frames feed their own
-        // tile times forward (PRT_FEEDBACK), which keeps the lists one frame old
-        if (!PRT_FEEDBACK && h.state == 2 && h.choice >= 0 && ++h.frames >= rt_ctx::Hybrid::REFRESH) h.state = 0;
-        if (h.state == 0) return Pick{0, 0};
-        if (h.state == 1) {
-            bool done = false;
-            if (hipError_t e = in_flight(h.ev, done); e != hipSuccess) return err(e, "rt_render: hybrid measurement");
-            if (!done) return Pick{1, h.choice >= 0 && h.pct[h.choice] == 0 ? h.cold[h.choice] : single_rule};
-            // the tile lists of every candidate threshold: [hot tiles][cold 8x8 tiles], one after another
-            const int tx = A.tiles_x, ty = A.n_tiles / A.tiles_x;
-            std::vector<long long> dur(h.n_tiles);
-            long long cmax = 1, dsum = 0;
-            for (size_t t = 0; t < h.n_tiles; t++) {
-                dur[t] = (long long)(h.h_tr[4 * t + 1] - h.h_tr[4 * t]);
-                cmax = std::max(cmax, dur[t]);
-                dsum += dur[t];
-            }
-            std::vector<int> ord = centre_out(tx, ty);
-            if (!dealt_centre_out)
-                for (int t = 0; t < (int)ord.size(); t++) ord[t] = t;  // RT_DEAL_ROW_MAJOR
-            h.cold_regions = xcd_mode >= 1 && xcd_mode <= 3 && dealt_centre_out;
-            h.cold_mode = h.cold_regions ? xcd_mode : 0;
-            const bool keep = h.choice >= 0;  // a refresh: new lists, the same candidates and choice
-            if (!keep) {
-                h.nc = 0;
-                auto add = [&](int pct, int lanes, int cold, bool lpt) {
-                    if (cold == RT_VARIANT_SHPOOL) cold = pool_v;  // (HYBRID_CANDS: "the pool kernel")
-                    if (h.nc >= rt_ctx::Hybrid::NCAND || !usable(cold)) return;
-                    h.pct[h.nc] = pct;
-                    h.lanes[h.nc] = lanes;
-                    h.lpt[h.nc] = lpt;
-                    h.cold[h.nc++] = cold;
-                };
-                if (f->hot_pct > 0) {
-                    add(f->hot_pct, f->hot_kernel == RT_HOT_COOP2 ? 2 : 4, RT_VARIANT_PERSIST, false);
-                } else {
-                    for (const HotCand& hc : HYBRID_CANDS) add(hc.pct, hc.lanes, hc.cold, hc.lpt);
-                }
-            }
-            std::vector<int> lists;
-            for (int c = 0; c < h.nc; c++) {
-                h.at[c] = lists.size();
-                h.n_hot[c] = h.n_cold[c] = 0;
-                if (h.pct[c] == 0 && !h.lpt[c]) continue;
-                std::vector<int> hot8;
-                for (size_t t = 0; t < h.n_tiles && h.pct[c] > 0; t++)
-                    if (dur[t] * 100 > (long long)h.pct[c] * cmax && dur[t] * (long long)h.n_tiles > 2 * dsum)
-                        hot8.push_back((int)t);  // (and over twice the mean: rt_feedback.hpp fb_tile)
-                std::stable_sort(hot8.begin(), hot8.end(), [&](int a, int b) { return dur[a] > dur[b]; });
-                if (hot8.size() > h.n_tiles / 2) hot8.resize(h.n_tiles / 2);  // k_coop costs ~2x the wave time
-                std::vector<char> is_hot(h.n_tiles, 0);
-                // each 8x8 tile = (8 / TW) x (8 / TH) tiles of the hot kernel (rtd::GTile), hottest first
-                int tw, th;
-                hot_tile(h.lanes[c], tw, th);
-                const int ctw = (f->width + tw - 1) / tw, cth = (f->n_rows + th - 1) / th;
-                for (int t : hot8) {
-                    is_hot[t] = 1;
-                    for (int qy = 0; qy < 8 / th; qy++)
-                        for (int qx = 0; qx < 8 / tw; qx++) {
-                            const int cx = (t % tx) * (8 / tw) + qx, cy = (t / tx) * (8 / th) + qy;
-                            if (cx < ctw && cy < cth) lists.push_back(cy * ctw + cx);
-                        }
-                }
-                h.n_hot[c] = (int)(lists.size() - h.at[c]);
-                std::vector<int> cold;
-                for (int t : ord)
-                    if (!is_hot[t]) cold.push_back(t);
-                if (h.lpt[c])  // costliest first (ties: centre-out)
-                    std::stable_sort(cold.begin(), cold.end(), [&](int a, int b) { return dur[a] > dur[b]; });
-                h.n_cold[c] = (int)cold.size();
-                if (h.cold_regions) cold = region_layout(cold, tx, ty, xcd_mode);
-                lists.insert(lists.end(), cold.begin(), cold.end());
-            }
-            if (!lists.empty()) {
-                // pinned staging: the last copy out of it ran before the measuring frame (stream order), which has
-                // finished; the device copy is stream-ordered after every frame that read the old lists
-                if (h.hl_cap < lists.size()) {
-                    if (h.h_lists) (void)hipHostFree(h.h_lists);
-                    h.h_lists = nullptr;
-                    h.hl_cap = 0;
-                    const hipError_t e = hipHostMalloc((void**)&h.h_lists, sizeof(int) * lists.size(), hipHostMallocDefault);
-                    if (e != hipSuccess) return err(e, "rt_render: hybrid lists");
-                    h.hl_cap = lists.size();
-                }
-                if (h.lists_cap < lists.size()) {  // (rare: a new shape; hipFree waits for the device)
-                    if (h.d_lists) (void)hipFree(h.d_lists);
-                    h.d_lists = nullptr;
-                    h.lists_cap = 0;
-                    const hipError_t e = hipMalloc((void**)&h.d_lists, sizeof(int) * lists.size());
-                    if (e != hipSuccess) return err(e, "rt_render: hybrid lists");
-                    h.lists_cap = lists.size();
-                }
-                std::memcpy(h.h_lists, lists.data(), sizeof(int) * lists.size());
-                const hipError_t e = hipMemcpyAsync(h.d_lists, h.h_lists, sizeof(int) * lists.size(),
-                                                    hipMemcpyHostToDevice, ctx->stream);
-                if (e != hipSuccess) return err(e, "rt_render: hybrid lists");
-            }
-            if (!keep) {
-                for (int c = 0; c < h.nc; c++)
-                    for (int r = 0; r < rt_ctx::Hybrid::ROUNDS; r++) h.launch[c][r] = -1;
-                h.choice = h.nc == 1 ? 0 : -1;
-            }
-            h.frames = 0;
-            h.state = 2;
-        }
-        auto pick_of = [&](int c) { return h.pct[c] == 0 && !h.lpt[c] ? Pick{1, h.cold[c]} : Pick{2, c}; };
-        if (h.choice >= 0) {
-            li.settled = 1;
-            li.trial = 0;
-            return pick_of(h.choice);
-        }
-        for (int c = 0; c < h.nc; c++)
-            for (int r = 0; r < rt_ctx::Hybrid::ROUNDS; r++)
-                if (h.launch[c][r] < 0 || ctx->launches - h.launch[c][r] >= rt_ctx::NEV) {  // untried (or events reused)
-                    h.launch[c][r] = ctx->launches;
-                    return pick_of(c);
-                }
-        long long last = 0;
-        for (int c = 0; c < h.nc; c++)
-            for (int r = 0; r < rt_ctx::Hybrid::ROUNDS; r++) last = std::max(last, h.launch[c][r]);
-        bool done = false;
-        if (hipError_t e = in_flight(ctx->ev1s[last % rt_ctx::NEV], done); e != hipSuccess) return err(e, "rt_render: hybrid trials");
-        if (!done) return Pick{1, single_rule};  // the trials are still running
-        int best = 0;
-        for (int c = 0; c < h.nc; c++) {
-            constexpr int W = rt_ctx::Hybrid::WARM, NT = rt_ctx::Hybrid::ROUNDS - W;
-            float t[NT];
-            for (int r = 0; r < NT; r++) {
-                const int sl = (int)(h.launch[c][W + r] % rt_ctx::NEV);
-                const hipError_t e = hipEventElapsedTime(&t[r], ctx->ev0s[sl], ctx->ev1s[sl]);
-                if (e != hipSuccess) return err(e, "rt_render: hybrid trials");
-            }
-            std::sort(t, t + NT);
-            h.ms[c] = t[NT / 2];  // the median of the timed trials
-            if (h.ms[c] < h.ms[best]) best = c;
-        }
-        h.choice = best;
-        h.frames = 0;
-        if (const char* l = std::getenv("PRT_TUNE_LOG"); l && std::atoi(l) == 1) {
-            std::fprintf(stderr, "[prt hybrid] %dx%d b%d:", f->width, f->n_rows, f->bounces);
-            for (int c = 0; c < h.nc; c++)
-                std::fprintf(stderr, " %s%d/coop%d/%s%s %.3f ms", h.pct[c] ? "hot>" : "whole", h.pct[c], h.lanes[c],
-                             variant_name(h.cold[c]), h.lpt[c] ? "/lpt" : "", h.ms[c]);
-            std::fprintf(stderr, " -> %d\n", best);
-        }
-        li.settled = 1;
-        li.trial = 0;
-        return pick_of(best);
-    };
-    // one frame of configuration (variant, cap); d_work holds the persistent grids' work counters, and the
-    // ray counters restart with every launch (rt_get_stats reports the frame, not the trial launches)
-    auto dispatch = [&](int md, int cp) -> int {
-        auto clear = [&]() -> int {
-            if (!ctx->batch_sum)  // a per-frame loop of a batch keeps adding to the batch's counters
-                HIPC(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * rtd::NCOUNT, ctx->stream));
-            HIPC(hipMemsetAsync(ctx->d_work, 0, 1024, ctx->stream));
-            return RT_OK;
-        };
-        // (a hybrid frame on device-built lists has its list builder clear them instead: after the pick)
-        if (!(PRT_FEEDBACK && md == RT_VARIANT_HYBRID))
-            if (int rc = clear()) return rc;
-        li.variant = md;
-        if (kernel == RT_KERNEL_STRICT) {
-            li.variant = 0;
-            auto k = count ? rtd::k_tiles<4, true, true> : rtd::k_tiles<4, true, false>;
-            if (f->bounces > 4) k = count ? rtd::k_tiles<8, true, true> : rtd::k_tiles<8, true, false>;
-            k<<<grid, rtd::BLOCK, 0, ctx->stream>>>(A);
-            return RT_OK;
-        }
-        if (md == RT_VARIANT_COOP2 || md == RT_VARIANT_COOP4) {
-            rtd::KArgs B = A;
-            const int gr = md == RT_VARIANT_COOP2 ? 2 : 4;
-            int tw, th;
-            hot_tile(gr, tw, th);  // rtd::GTile<gr>
-            B.tiles_x = (f->width + tw - 1) / tw;
-            const int ty = (f->n_rows + th - 1) / th;
-            B.n_tiles = B.tiles_x * ty;
-            if (int rc = order_for(B.tiles_x, ty, B.tile_order)) return rc;
-            return f->bounces <= 4 ? launch_group<4>(B, gr, count, ctx->device, ctx->stream, cp)
-                                   : launch_group<8>(B, gr, count, ctx->device, ctx->stream, cp);
-        }
-        rtd::KArgs P = A;
-        if (region_off) {
-            P.region_off = region_off;
-            P.tile_order = region_order;
-        }
-        if (md == RT_VARIANT_HYBRID) {
-            int rc = RT_OK;
-            const Pick pk = hybrid_pick(rc);
-            if (rc) return rc;
-            rt_ctx::Hybrid& h = ctx->hy;
-            const bool fb = PRT_FEEDBACK && pk.kind == 2 && h.fb_ok && h.d_cost;
-            if (PRT_FEEDBACK && !fb)
-                if (int rc2 = clear()) return rc2;
-            // the frame's HIP-event time starts here, after the host work of the pick (the trials compare them)
-            HIPC(hipEventRecord(ctx->ev0, ctx->stream));
-            // every frame of the shape records its tiles' durations (rt_feedback.hpp); a hybrid candidate's frame --
-            // tried or chosen -- builds its lists from the previous frame's first, on the device (the memset follows
-            // that build: k_coop's hot tiles combine their group tiles' times by atomic max). The trials too: with a
-            // moving camera the measuring frame's lists age frame by frame, and a candidate tried later would be
-            // priced with older lists than one tried first (a car_boxed walkthrough settled on the wrong candidate).
-            if (PRT_FEEDBACK && h.d_cost) {
-                if (fb) {
-                    li.hot_pct = h.pct[pk.c];
-                    li.hot_lanes = h.lanes[pk.c];
-                    li.cold_variant = h.cold[pk.c];
-                    const int r2 = f->bounces <= 4 ? launch_hybrid_fb<4>(ctx, A, count, pk.c, &li.build)
-                                                   : launch_hybrid_fb<8>(ctx, A, count, pk.c, &li.build);
-                    h.fb_ok = r2 == RT_OK;
-                    return r2;
-                }
-                unsigned* w = h.cost_at(h.cost_cur ^ 1);
-                HIPC(hipMemsetAsync(w, 0, sizeof(unsigned) * (h.n_tiles + 1), ctx->stream));
-                P.tile_cost = w;
-                A.tile_cost = w;
-                h.cost_cur ^= 1;
-                h.fb_ok = true;  // (this frame, in stream order, fills it)
-            }
-            if (pk.kind == 2) {
-                li.hot_pct = ctx->hy.pct[pk.c];
-                li.hot_lanes = ctx->hy.lanes[pk.c];
-                li.cold_variant = ctx->hy.cold[pk.c];
-                return f->bounces <= 4 ? launch_hybrid<4>(ctx, A, count, pk.c, &li.build)
-                                       : launch_hybrid<8>(ctx, A, count, pk.c, &li.build);
-            }
-            if (pk.kind == 0) {  // measuring frame: k_persist with per-tile times, copied to the host behind it
-                li.variant = RT_VARIANT_PERSIST;
-                li.refresh = h.choice >= 0 ? 1 : 0;  // a decided shape's periodic list refresh (settled)
-                li.trial = li.refresh ? 0 : 1;
-                li.settled = li.refresh;
-                P.tile_trace = h.d_tr;
-                if (f->bounces <= 4) launch_paths<4>(P, RT_VARIANT_PERSIST, count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
-                else launch_paths<8>(P, RT_VARIANT_PERSIST, count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
-                HIPC(hipGetLastError());
-                HIPC(hipMemcpyAsync(h.h_tr, h.d_tr, sizeof(unsigned long long) * 4 * h.n_tiles, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-                HIPC(hipEventRecord(h.ev, ctx->stream));
-                h.state = 1;
-                return RT_OK;
-            }
-            md = pk.c;  // a whole-frame kernel: chosen, tried, or while the measurement / trials are on their way
-            li.variant = md;
-        }
-        if (f->bounces <= 4) launch_paths<4>(P, md, count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
-        else launch_paths<8>(P, md, count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
-        return RT_OK;
-    };
-    {
-        HIPC(hipEventRecord(ctx->ev0, ctx->stream));
-        const int rc = dispatch(mode, cap);
-        if (rc) return rc;
-    }
+    if (int rc = tile_orders(ctx, L)) return rc;
+    L.caps = launch_caps(ctx, L);
+    int mode = rtl::resolve_variant(L.caps, f->variant);
+    L.li.settled = 1;
+    // the measured rule of frame batches and spp > 1, where the pool can run and nothing forbids trials
+    if (f->variant == RT_VARIANT_DEFAULT && L.kernel == RT_KERNEL_FAST && !A.tile_trace && !L.count &&
+        (n_frames > 1 || f->spp > 1) && L.caps.shp_ok)
+        if (int rc = batch_rule_pick(ctx, L, mode)) return rc;
+    HIPC(hipEventRecord(ctx->ev0, ctx->stream));
+    if (int rc = dispatch(ctx, L, mode, f->waves_cap)) return rc;
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(ctx->ev1, ctx->stream));
-    if (d_trace) {
-        std::vector<unsigned long long> h(4 * trace_n);
-        HIPC(hipStreamSynchronize(ctx->stream));
-        HIPC(hipMemcpy(h.data(), d_trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-        HIPC(hipFree(d_trace));
-        if (FILE* fp = std::fopen(trace_path, "wb")) {
-            std::fwrite(h.data(), sizeof(unsigned long long), h.size(), fp);
-            std::fclose(fp);
-        }
-    }
-    ctx->last_launch = li;
+    if (d_trace)
+        if (int rc = write_tile_trace(ctx, d_trace, trace_n, trace_path)) return rc;
+    ctx->last_launch = L.li;
     ctx->launches++;
     ctx->last_rgb = rgb;
     ctx->last_bgra = bgra;
@@ -1984,8 +1964,8 @@ int render_batch(rt_ctx* ctx, const rt_camera* cams, int n_frames, const rt_fram
     ctx->last_off = f->row_offset;
     ctx->last_stride = f->row_stride;
     ctx->last_rows = f->n_rows;
-    ctx->last_block = rb;
-    ctx->last_shift = fs;
+    ctx->last_block = A.row_block;
+    ctx->last_shift = f->frame_shift;
     ctx->rendered = true;
     return RT_OK;
 }
@@ -2052,15 +2032,7 @@ extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results
     if (r->n == 0) return RT_OK;
     rtd::QArgs A;
     std::memset(&A, 0, sizeof A);
-    A.s.ref = dview(ctx->ref);
-    A.s.acc = ctx->acc.nodes ? dview(ctx->acc) : A.s.ref;
-    A.s.wide = rtd::DWide{ctx->wide_nodes, ctx->wide_tris, ctx->wide_orig, ctx->wide_n};
-    A.s.unit = rtd::DWide{ctx->unit_nodes, ctx->unit_tris, ctx->unit_orig, ctx->unit_n};
-    A.s.prim = rtd::DWide{ctx->prim_nodes, ctx->prim_tris, ctx->prim_orig, ctx->prim_n};  // chosen per ray
-    A.s.faces = ctx->d_faces;
-    A.s.ref_path = ctx->ref.path;
-    A.s.n_tris = ctx->n_tris;
-    for (int a = 0; a < 3; a++) A.s.n_face[a] = (int)ctx->faces[a].size();
+    A.s = scene_args(ctx);  // (the primary view is chosen per ray)
     A.origin = r->origin;
     A.dir = r->dir;
     A.max_dist2 = r->max_dist2;
@@ -2074,7 +2046,7 @@ extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results
     const bool strict = r->kernel == RT_KERNEL_STRICT;
     // the pool form (rt_query.hpp occluded_pool): the fast occlusion query on a wide view; regroup = its refill
     // threshold in idle lanes (0: 16), 64 = the lockstep form instead. The closest-hit query has the lockstep form only.
-    const bool pool = r->kind == RT_QUERY_OCCLUDED && !strict && ctx->wide_n > 0 && r->regroup != 64;
+    const bool pool = r->kind == RT_QUERY_OCCLUDED && !strict && ctx->wide.n > 0 && r->regroup != 64;
     A.regroup = r->regroup > 0 ? r->regroup : 16;
     const QFn k = query_kernel(r->kind, strict, ctx->tq_ok, pool);
     const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
@@ -2197,158 +2169,6 @@ int grow(rt_ctx* ctx, T** p, size_t& cap, size_t n) {
     cap = 0;
     HIPC(hipMalloc((void**)p, sizeof(T) * std::max<size_t>(n, 1)));
     cap = n;
-    return RT_OK;
-}
-}  // namespace
-
-namespace {
-// RT_VARIANT_HYBRID, one frame: the hot tiles (ctx->hy lists) through k_coop on the context's second stream
-// while the cold kernel (k_persist, or the shadow pool) renders the cold 8x8 tiles on the context stream; both
-// persistent grids together fill the chip (the hot grid is sized to start every hot tile at once, at most half the
-// chip), and the context stream waits for both.
-template <int MAXB>
-int launch_hybrid(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build) {
-    rt_ctx::Hybrid& h = ctx->hy;
-    const int n_hot = h.n_hot[c], n_cold = h.n_cold[c];
-    int* lists = h.d_lists + h.at[c];
-    const int g = h.lanes[c];
-    const KFn kc = coop_kernel<MAXB>(g, count);
-    int tw, th;
-    hot_tile(g, tw, th);
-    rtd::KArgs B = A;  // the hot kernel's tiles, dealt hottest first from their own work counter
-    B.tiles_x = (A.W + tw - 1) / tw;
-    B.n_tiles = n_hot;
-    B.tile_order = lists;
-    B.region_off = nullptr;
-    B.work = A.work + 224;
-    rtd::KArgs P = A;
-    P.n_tiles = n_cold;
-    P.region_off = h.cold_regions ? lists + n_hot : nullptr;
-    P.tile_order = lists + n_hot + (h.cold_regions ? 9 : 0);
-    size_t dyn = 0;
-    const KFn kp = persist_kernel<MAXB>(P, h.cold[c], count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
-    const int rp = resident(kp, ctx->device, 8, dyn);
-    const int rcp = resident(kc, ctx->device);
-    const int nc = n_hot > 0 ? std::max(1, std::min((n_hot + 3) / 4, rcp / 2)) : 0;
-    const int np = std::max(1, std::min(rp - (int)((long long)nc * rp / rcp), (n_cold + 3) / 4));
-    if (n_hot == 0) {  // (a whole frame in the measured order)
-        if (n_cold > 0) kp<<<np, rtd::BLOCK, dyn, ctx->stream>>>(with_slots(P, dyn));
-        HIPC(hipGetLastError());
-        return RT_OK;
-    }
-    HIPC(hipEventRecord(h.fork, ctx->stream));  // after the work / counter resets
-    HIPC(hipStreamWaitEvent(h.s2, h.fork, 0));
-    if (n_hot > 0) kc<<<nc, rtd::BLOCK, 0, h.s2>>>(B);
-    HIPC(hipGetLastError());
-    if (n_cold > 0) kp<<<np, rtd::BLOCK, dyn, ctx->stream>>>(with_slots(P, dyn));
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(h.join, h.s2));
-    HIPC(hipStreamWaitEvent(ctx->stream, h.join, 0));
-    return RT_OK;
-}
-
-// A decided shape's frame under the per-frame feedback (rt_feedback.hpp): candidate c's lists built on the device from
-// the previous frame's tile durations (k_fb_max, k_fb_count, k_fb_place), the durations cleared, then c's kernels as launch_hybrid launches
-// them, every one reading its list and count from the device and recording this frame's durations. The grids are sized
-// by a recent frame's hot count, read back without a wait.
-template <int MAXB>
-int launch_hybrid_fb(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned* build) {
-    rt_ctx::Hybrid& h = ctx->hy;
-    const int g = h.lanes[c] == 2 ? 2 : 4;
-    const bool hot = h.pct[c] > 0;
-    int tw, th;
-    hot_tile(g, tw, th);
-    const int ctw = (A.W + tw - 1) / tw, cth = (A.n_rows + th - 1) / th;
-    int* d_hot = h.d_fb;
-    int* d_cold = h.d_fb + 4 * h.n_tiles;
-    int* d_cnt = d_cold + 9 + h.n_tiles;
-    const int tx = A.tiles_x, ty = A.n_tiles / A.tiles_x;
-    if (h.info_mode != h.cold_mode) {  // the shape's per-tile region and hot-kernel tile counts, once
-        std::vector<unsigned char> info(h.n_tiles);
-        for (int t = 0; t < A.n_tiles; t++) info[t] = rtd::fb_tile_info(t, tx, ty, h.cold_mode, A.W, A.n_rows);
-        HIPC(hipMemcpy(h.d_info, info.data(), info.size(), hipMemcpyHostToDevice));
-        h.info_mode = h.cold_mode;
-    }
-    // (hot set: at most half the 8x8 tiles, as the host's lists, counted in hot-kernel tiles)
-    // (d_cost holds n_tiles + 1 words: A.n_tiles is this shape's n_tiles, the maximum's word right after the tiles)
-    // the last frame's times in, this frame's buffer cleared by k_fb_max (with the frame's counters and work words)
-    unsigned* const cost_in = h.cost_at(h.cost_cur);
-    unsigned* const cost_out = h.cost_at(h.cost_cur ^ 1);
-    rtd::FbArgs F{cost_in, A.n_tiles, tx, ty, h.pct[c], (int)(h.n_tiles / 2) * (8 / tw) * (8 / th), tw, th, ctw, cth, h.cold_mode,
-                  h.d_info, d_hot, d_cold, d_cnt, (unsigned*)(d_cnt + 4), (unsigned*)(d_cnt + 4) + rtd::FB_G * rtd::FB_TK, 0,
-                  cost_out,
-                  ctx->batch_sum ? nullptr : ctx->d_counters, rtd::NCOUNT, ctx->d_work, 1024 / 4};
-    {  // the camera against the last feedback frame's (rt_feedback.hpp FbArgs::moved)
-        float cam[12];
-        std::memcpy(cam, A.pos, sizeof(float) * 3);
-        std::memcpy(cam + 3, A.ul, sizeof(float) * 3);
-        std::memcpy(cam + 6, A.ix, sizeof(float) * 3);
-        std::memcpy(cam + 9, A.iy, sizeof(float) * 3);
-        F.moved = h.fb_cam_ok && std::memcmp(cam, h.fb_cam, sizeof cam) != 0;
-        std::memcpy(h.fb_cam, cam, sizeof cam);
-        h.fb_cam_ok = true;
-    }
-    rtd::k_fb_max<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
-    rtd::k_fb_count<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
-    rtd::k_fb_place<<<rtd::FB_G, rtd::FB_THREADS, 0, ctx->stream>>>(F);
-    HIPC(hipGetLastError());
-    h.cost_cur ^= 1;
-    if (h.fb_pending) {  // a recent frame's hot count (grid size), if its copy has landed: a query, never a wait
-        const hipError_t q = hipEventQuery(h.fb_ev);
-        if (q == hipSuccess) {
-            h.fb_hot_est = h.h_fb_cnt[0];
-            h.fb_est_c = h.fb_pend_c;
-            h.fb_pending = false;
-        } else if (q == hipErrorNotReady) {
-            (void)hipGetLastError();
-        } else {
-            return fail(ctx, q, "rt_render: hybrid feedback count");
-        }
-    }
-    if (hot && !h.fb_pending) {
-        HIPC(hipMemcpyAsync(h.h_fb_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIPC(hipEventRecord(h.fb_ev, ctx->stream));
-        h.fb_pending = true;
-        h.fb_pend_c = c;
-    }
-    const KFn kc = coop_kernel<MAXB>(g, count);
-    rtd::KArgs B = A;  // the hot kernel's tiles, hottest first, their number on the device
-    B.tiles_x = ctw;
-    B.n_tiles = 4 * (int)h.n_tiles;
-    B.n_tiles_dev = d_cnt;
-    B.tile_order = d_hot;
-    B.region_off = nullptr;
-    B.work = A.work + 224;
-    B.tile_cost = cost_out;
-    rtd::KArgs P = A;  // the cold 8x8 tiles by region, costliest first (the region offsets hold their number)
-    P.region_off = d_cold;
-    P.tile_order = d_cold + 9;
-    P.tile_cost = cost_out;
-    size_t dyn = 0;
-    const KFn kp = persist_kernel<MAXB>(P, h.cold[c], count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
-    if (build) *build |= RT_BUILD_FEEDBACK;
-    const int rp = resident(kp, ctx->device, 8, dyn);
-    const int rcp = resident(kc, ctx->device);
-    const int est = h.fb_hot_est >= 0 && h.fb_est_c == c ? h.fb_hot_est : h.n_hot[c];  // (another candidate's: its own)
-    // the hot kernel's grid from a count a few frames old: with headroom (2x + 64 tiles), since a hot set that grew
-    // past its grid's waves -- a moving camera's, after frames of few hot tiles -- is rendered by too few waves (dragon
-    // walkthrough frames of 3-6 ms among ~1.1 ms ones); a persistent grid's waves that find no tile exit at once
-    const int est_h = 2 * est + 64;
-    const int nc = hot ? std::max(1, std::min((est_h + 3) / 4, rcp / 2)) : 0;
-    const int np = std::max(1, std::min(rp - (int)((long long)nc * rp / rcp), (A.n_tiles + 3) / 4));
-    if (!hot) {  // (the whole frame, costliest first)
-        kp<<<np, rtd::BLOCK, dyn, ctx->stream>>>(with_slots(P, dyn));
-        HIPC(hipGetLastError());
-        return RT_OK;
-    }
-    HIPC(hipEventRecord(h.fork, ctx->stream));  // after the lists, the counters' and the durations' resets
-    HIPC(hipStreamWaitEvent(h.s2, h.fork, 0));
-    kc<<<nc, rtd::BLOCK, 0, h.s2>>>(B);
-    HIPC(hipGetLastError());
-    kp<<<np, rtd::BLOCK, dyn, ctx->stream>>>(with_slots(P, dyn));
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(h.join, h.s2));
-    HIPC(hipStreamWaitEvent(ctx->stream, h.join, 0));
     return RT_OK;
 }
 }  // namespace
