@@ -324,6 +324,45 @@ typedef struct rt_query_info {
  * valid), RT_E_STATE before the first query */
 int rt_get_query_info(rt_ctx* ctx, rt_query_info* info);
 
+/* Radiance queries: the reference's raytrace() (cpu/src/raytracer.c:101-177) for the caller's own rays -- Lambert/Blinn
+ * shading with one shadow ray per light, the reflection chain of `bounces` levels, folded deepest level first -- so a
+ * ray no pinhole camera on a pixel grid expresses (a panorama, an orthographic view, jittered samples, a probe) gets
+ * the colour, bit for bit, that a frame's pixel with that primary ray would get. RT_KERNEL_FAST answers with the same
+ * bits as RT_KERNEL_STRICT: the caller's ray is tested as rt_trace_rays tests it, and a path whose first ray is outside
+ * the fast walks' domain walks the reference tree at every level. No ray value is an error.
+ * A shade query touches nothing a render call owns (as rt_trace_rays) and leaves rt_get_query_info's answer alone. */
+typedef struct rt_shade {
+    const float* origin;   /* device, [n][3] f32 */
+    const float* dir;      /* device, [n][3] f32, NOT normalised by the library */
+    int n;                 /* >= 0; 0 is RT_OK and launches nothing */
+    int bounces;           /* 1..8, as rt_frame.bounces */
+    int kernel;            /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+    int regroup;           /* fast kernel's shadow-pool form: 1..63 idle lanes per refill; 0 = library default;
+                              64 = the lockstep form. Same bits either way. */
+    int unclamped;         /* 0: rgb = vec_constrain(raytrace(o, d, 0), 0, 1), a frame's pixel;
+                              1: raytrace()'s return value as is (rgb only; refused together with bgra) */
+} rt_shade;
+typedef struct rt_shade_results {   /* device pointers, all nullable, at least one non-null when n > 0 */
+    float* rgb;            /* [n][3] */
+    unsigned int* bgra;    /* [n], vec_to_bgra's quantisation as rt_outputs.bgra */
+    int* hit; float* t;    /* [n] the level-0 closest hit, exactly rt_trace_rays' CLOSEST answer */
+    int* bounce_hit;       /* [n][bounces], -1 miss, -2 level not reached, as rt_outputs.bounce_hit */
+} rt_shade_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written */
+int rt_shade_rays(rt_ctx* ctx, const rt_shade* rays, const rt_shade_results* out);
+typedef struct rt_shade_info {
+    long long rays, hits, reflection, shadow, shadow_skipped; /* rt_stats' primary / hits / reflection / shadow /
+                                  shadow_skipped, for this query: rays = the caller's (level-0) rays */
+    long long strict_paths;    /* fast kernel: paths whose level-0 ray is outside the fast walks' domain */
+    long long tie_rewalks;     /* fast walks re-walked on the reference tree (an exact tie, a failed reference-path
+                                  check, a degenerate ray on a box face), at any level */
+    long long stack_overflows; /* must be 0 */
+    float kernel_ms;           /* HIP events around the query's launch */
+} rt_shade_info;
+/* counters of the last shade query (synchronises); RT_E_KERNEL when it overflowed a traversal stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info);
+
 /* load_from_gpu(): copies the last frame's compact rows to host (synchronous); nullable args. RT_E_KERNEL when the
  * render reported a traversal-stack overflow (its frame is not valid). */
 int rt_download(rt_ctx* ctx, float* h_rgb, int* h_hit);

@@ -32,6 +32,7 @@
 #include "rt_treelet.hpp"
 #include "rt_feedback.hpp"
 #include "rt_query.hpp"
+#include "rt_shade.hpp"
 #ifndef PRT_TREELET
 #define PRT_TREELET 2  // treelet-restructuring passes over the GPU-built binary tree (0: none)
 #endif
@@ -175,6 +176,12 @@ struct rt_ctx {
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
     bool queried = false, q_launched = false;
     std::unordered_map<const void*, int> q_resident;  // resident workgroups of each k_query instantiation (resident())
+    // radiance queries (rt_shade_rays, rt_shade.hpp): the same again, their own ([rtd::S_NCOUNT] counters, then the
+    // chunk counter) -- a shade query touches neither a render's state nor rt_get_query_info's answer
+    unsigned long long* d_shq = nullptr;
+    hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
+    bool shaded = false, s_launched = false;
+    std::unordered_map<const void*, int> s_resident;  // resident workgroups of each k_shade instantiation (0: none fits)
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -2089,6 +2096,140 @@ extern "C" int rt_get_query_info(rt_ctx* ctx, rt_query_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- radiance queries (rt_shade.hpp)
+namespace {
+using SFn = void (*)(rtd::SArgs);
+template <int MAXB>
+SFn shade_kernel_of(bool strict, bool tq, bool pool) {
+    using rtd::k_shade;
+    if (strict) return k_shade<MAXB, true, false, false>;
+    if (pool) return tq ? k_shade<MAXB, false, true, true> : k_shade<MAXB, false, false, true>;
+    return tq ? k_shade<MAXB, false, true, false> : k_shade<MAXB, false, false, false>;
+}
+SFn shade_kernel(int bounces, bool strict, bool tq, bool pool) {
+    return FOR_MAXB(bounces, shade_kernel_of, strict, tq, pool);
+}
+template <int MAXB>
+size_t shade_lds_of(bool tq) { return rtd::shade_pool_lds<MAXB>(tq); }
+size_t shade_lds(int bounces, bool tq) { return FOR_MAXB(bounces, shade_lds_of, tq); }
+// resident workgroups of a k_shade instantiation with `dyn` bytes of dynamic LDS (asked once per kernel); 0: a
+// workgroup of it does not fit a CU
+int shade_resident(rt_ctx* ctx, SFn k, size_t dyn) {
+    auto res = ctx->s_resident.find((const void*)k);
+    if (res != ctx->s_resident.end()) return res->second;
+    int per_cu = 0;
+    const bool fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, rtd::BLOCK, dyn) == hipSuccess && per_cu >= 1;
+    (void)hipGetLastError();
+    const int n = fits ? resident(k, ctx->device, 8, dyn) : 0;
+    ctx->s_resident.emplace((const void*)k, n);
+    return n;
+}
+// The library's choice for regroup = 0: the pool form at 16 idle lanes (measured, DESIGN.md §3l: 28 % less time than
+// the lockstep form on dragon's row-major camera rays, 3 % more on car_boxed's).
+constexpr int SHADE_REGROUP_DEFAULT = 16;
+}  // namespace
+
+extern "C" int rt_shade_rays(rt_ctx* ctx, const rt_shade* r, const rt_shade_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_shade_rays: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_shade_rays: null rays / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_shade_rays: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_shade_rays: negative ray count");
+    if (r->bounces < 1 || r->bounces > 8) return arg_err(ctx, "rt_shade_rays: bounces must be 1..8");
+    if (r->regroup < 0 || r->regroup > 64) return arg_err(ctx, "rt_shade_rays: regroup must be 0..64");
+    if (r->unclamped != 0 && r->unclamped != 1) return arg_err(ctx, "rt_shade_rays: unclamped must be 0 or 1");
+    if (r->unclamped && out->bgra) return arg_err(ctx, "rt_shade_rays: unclamped has no bgra quantisation");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_shade_rays: null origin / dir");
+    if (r->n > 0 && !out->rgb && !out->bgra && !out->hit && !out->t && !out->bounce_hit)
+        return arg_err(ctx, "rt_shade_rays: no output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::S_NCOUNT + 1);
+    if (!ctx->d_shq) HIPC(hipMalloc((void**)&ctx->d_shq, cbytes));
+    if (!ctx->s_ev0) HIPC(hipEventCreate(&ctx->s_ev0));
+    if (!ctx->s_ev1) HIPC(hipEventCreate(&ctx->s_ev1));
+    HIPC(hipMemsetAsync(ctx->d_shq, 0, cbytes, ctx->stream));
+    ctx->shaded = true;
+    ctx->s_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::SArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the primary view is chosen per ray)
+    A.origin = r->origin;
+    A.dir = r->dir;
+    A.rgb = out->rgb;
+    A.bgra = out->bgra;
+    A.hit = out->hit;
+    A.t = out->t;
+    A.bounce_hit = out->bounce_hit;
+    A.counters = ctx->d_shq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_shq + rtd::S_NCOUNT);
+    A.n = r->n;
+    A.bounces = r->bounces;
+    A.o_max = 4.0f * ctx->scene_mx;
+    A.unclamped = r->unclamped;
+    const bool strict = r->kernel == RT_KERNEL_STRICT;
+    // the pool form (rt_shade.hpp shade_pool): the fast kernel on a wide view whose lights fit trace_path_dfr's 8-bit masks
+    // and whose nodes fit the pool's packed stack entries; regroup = its refill threshold, 64 = the lockstep form
+    const int regroup = r->regroup > 0 ? r->regroup : SHADE_REGROUP_DEFAULT;
+    bool pool = !strict && regroup != 64 && ctx->wide.n > 0 && ctx->n_lights <= 8 && ctx->pk_ok;
+    A.regroup = regroup;
+    SFn k = nullptr;
+    size_t dyn = 0;
+    int res = 0;
+    if (pool) {
+        k = shade_kernel(r->bounces, false, ctx->tq_ok, true);
+        dyn = shade_lds(r->bounces, ctx->tq_ok);
+        res = shade_resident(ctx, k, dyn);
+        if (res == 0) pool = false;  // its LDS does not fit: the lockstep form
+    }
+    if (!pool) {
+        k = shade_kernel(r->bounces, strict, ctx->tq_ok, false);
+        dyn = 0;
+        res = shade_resident(ctx, k, 0);
+        if (res == 0) return arg_err(ctx, "rt_shade_rays: the kernel does not fit this device");
+    }
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    const int blocks = std::max(1, std::min(res, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->s_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, dyn, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->s_ev1, ctx->stream));
+    ctx->s_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->shaded) {
+        ctx->err = "rt_get_shade_info: no rays shaded";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::S_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_shq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->rays = (long long)c[rtd::S_RAYS];
+    info->hits = (long long)c[rtd::S_HITS];
+    info->reflection = (long long)c[rtd::S_REFL];
+    info->shadow = (long long)c[rtd::S_SHAD];
+    info->shadow_skipped = (long long)c[rtd::S_SKIP];
+    info->strict_paths = (long long)c[rtd::S_STRICT];
+    info->tie_rewalks = (long long)c[rtd::S_TIE];
+    info->stack_overflows = (long long)c[rtd::S_ERR];
+    if (ctx->s_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->s_ev0, ctx->s_ev1));
+    if (c[rtd::S_ERR]) {
+        ctx->err = "rt_get_shade_info: the query's traversal stack overflowed " + std::to_string(c[rtd::S_ERR]) +
+                   " times (BVH deeper than the walks' stacks): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -2933,6 +3074,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_query) (void)hipFree(ctx->d_query);
     if (ctx->q_ev0) (void)hipEventDestroy(ctx->q_ev0);
     if (ctx->q_ev1) (void)hipEventDestroy(ctx->q_ev1);
+    if (ctx->d_shq) (void)hipFree(ctx->d_shq);
+    if (ctx->s_ev0) (void)hipEventDestroy(ctx->s_ev0);
+    if (ctx->s_ev1) (void)hipEventDestroy(ctx->s_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

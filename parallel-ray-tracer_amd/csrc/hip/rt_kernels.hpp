@@ -1378,13 +1378,23 @@ __device__ __forceinline__ void seti(int (&a)[MAXB], int i, int v) {
 // register arrays (cold values: written once per level, read once by the fold), which frees 4 * MAXB
 // registers across the walks for the kernels with the tightest register budget.
 // PK / TQ: packed stack entries and packed triangle tests (the SHP = 3 build of PERSIST4; tq: the wave's queue)
+// path_step is two halves: the level's closest hit (path_step itself) and everything after it (path_shade: the miss
+// colour, Lambert/Blinn with the shadow rays, the reflection ray, the path's end). A caller that finds a level's
+// closest hit its own way (k_shade's level 0, rt_shade.hpp: closest_q on a caller-supplied ray) shades it with
+// path_shade, so the shading arithmetic exists once.
+template <int MAXB, bool STRICT, bool COUNT, bool REG, int G = 1, bool PB = false, bool PK = false, bool TQ = false>
+__device__ __forceinline__ bool path_shade(const DScene& s, int bounces, int it, int orig, float best, int nd, v3& o,
+                                           v3& d, v3 (&cols)[MAXB], int (&mats)[MAXB], int& L, bool& tail,
+                                           int* __restrict__ stk, Ctr& c, unsigned q = 0,
+                                           float4* __restrict__ pb = nullptr, int* __restrict__ sstk = nullptr,
+                                           int wcap = WSTACK, int* tq = nullptr);
+
 template <int MAXB, bool STRICT, bool COUNT, bool REG, int G = 1, bool PB = false, bool PK = false, bool TQ = false>
 __device__ __forceinline__ bool path_step(const DScene& s, int bounces, int it, v3& o, v3& d, v3 (&cols)[MAXB],
                                           int (&mats)[MAXB], int& L, bool& tail, int& hit0, float& t0,
                                           int* __restrict__ bh, int bh_pix, int* __restrict__ stk, Ctr& c,
                                           unsigned q = 0, float4* __restrict__ pb = nullptr,
                                           int* __restrict__ sstk = nullptr, int wcap = WSTACK, int* tq = nullptr) {
-    const v3 amb = mk(s.amb_x, s.amb_y, s.amb_z);
     float best;
     int nd;
     if (COUNT) c.lvl = (unsigned)it;
@@ -1398,6 +1408,17 @@ __device__ __forceinline__ bool path_step(const DScene& s, int bounces, int it, 
         t0 = best;
     }
     if (bh && bh_pix >= 0) bh[(size_t)opaque(bh_pix) * bounces + it] = orig;  // per-level dump (uniform base, nullable)
+    return path_shade<MAXB, STRICT, COUNT, REG, G, PB, PK, TQ>(s, bounces, it, orig, best, nd, o, d, cols, mats, L, tail,
+                                                               stk, c, q, pb, sstk, wcap, tq);
+}
+
+// The level's colour from its closest hit (orig: the original triangle or -1, best: its t, nd: the side hit)
+template <int MAXB, bool STRICT, bool COUNT, bool REG, int G, bool PB, bool PK, bool TQ>
+__device__ __forceinline__ bool path_shade(const DScene& s, int bounces, int it, int orig, float best, int nd, v3& o,
+                                           v3& d, v3 (&cols)[MAXB], int (&mats)[MAXB], int& L, bool& tail,
+                                           int* __restrict__ stk, Ctr& c, unsigned q, float4* __restrict__ pb,
+                                           int* __restrict__ sstk, int wcap, int* tq) {
+    const v3 amb = mk(s.amb_x, s.amb_y, s.amb_z);
     if (orig < 0) {  // raytracer.c:132-135
         if constexpr (PB) pb[it * 64] = make_float4(0.0f + amb.x, 0.0f + amb.y, 0.0f + amb.z, __int_as_float(0));
         else set3<MAXB>(cols, it, mk(0.0f + amb.x, 0.0f + amb.y, 0.0f + amb.z));

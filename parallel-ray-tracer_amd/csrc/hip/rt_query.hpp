@@ -91,12 +91,14 @@ __device__ __forceinline__ bool shadow_domain(v3 o, v3 d, float ld2, float o_max
 // degenerate ray on a face checked by ref_reaches), with the view chosen per ray and the domain tested first. The
 // fast walks keep their view in scalar registers (walk_base), so the wave walks the views its rays chose one after
 // another (a coherent ray set chooses one); the rays handed back and the rays outside the domain then walk the
-// reference tree together.
+// reference tree together. nd: the side of the winning triangle the ray hit (the walk's that answered), which a
+// caller that shades the hit needs (rt_shade.hpp) and the closest-hit query does not.
 template <bool TQ>
-__device__ __forceinline__ int closest_q(const DScene& s, v3 o, v3 d, float o_max, float& best, int* __restrict__ stk,
-                                         Ctr& c, unsigned& ev, int* tq) {
-    int hp = -1, nd = 0, orig = -1;
+__device__ __forceinline__ int closest_q(const DScene& s, v3 o, v3 d, float o_max, float& best, int& nd,
+                                         int* __restrict__ stk, Ctr& c, unsigned& ev, int* tq) {
+    int hp = -1, orig = -1;
     bool tie = false, done = false;
+    nd = 0;
     best = FMAX;
     const bool dom = query_domain(o, d, o_max);
     const bool face = degenerate(d) && !degenerate_ok(s, o, d);
@@ -145,6 +147,12 @@ __device__ __forceinline__ int closest_q(const DScene& s, v3 o, v3 d, float o_ma
     nd = 0;
     closest_walk<true, false>(s.ref, o, d, best, hp, nd, tie, stk, c);
     return hp >= 0 ? s.ref.tri_orig[hp] : -1;
+}
+template <bool TQ>
+__device__ __forceinline__ int closest_q(const DScene& s, v3 o, v3 d, float o_max, float& best, int* __restrict__ stk,
+                                         Ctr& c, unsigned& ev, int* tq) {
+    int nd;
+    return closest_q<TQ>(s, o, d, o_max, best, nd, stk, c, ev, tq);
 }
 
 // visible() for a query ray

@@ -406,18 +406,37 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
 // own direction: the primary one, then each level's reflection, recomputed), then the deepest-first fold. The path
 // buffer holds a level's hit point and visibility word (then its colour and material), and a second [level][lane]
 // array its hit triangle (orig | nd << 30, -1: a miss).
-template <int MAXB, bool COUNT>
-__device__ __forceinline__ v3 trace_path_dfr(const KArgs& A, bool alive, v3 o, v3 d, int* __restrict__ stk, Ctr& c,
-                                             UCtr& u, int hpix, int* __restrict__ sstk, int wcap) {
-    extern __shared__ int lds_dyn[];
-    float4* pb0 = (float4*)(lds_dyn + wstack_words(wcap, true) * BLOCK);
-    const size_t wl = (size_t)((threadIdx.x >> 6) * MAXB) * 64 + (threadIdx.x & 63);
-    float4* pb = pb0 + wl;
-    float4* pbw = pb - (threadIdx.x & 63);  // the wave's slots of level 0
-    int* hid = (int*)(pb0 + (size_t)BLOCK * MAXB) + wl;
-    // the wave's packed-triangle queue (TQ_*): the closest walks' result slots empty, its counter 0
-    int* tq = (int*)(pb0 + (size_t)BLOCK * MAXB) + BLOCK * MAXB + (threadIdx.x >> 6) * TQ_WORDS;
-    tq_clear(tq);
+// Q: whose path it is. FramePath: a frame kernel's pixel (the PB = 2 LDS layout, closest(), the frame's hit / t /
+// bounce_hit at hpix) -- every statement the frame kernels had, under `if constexpr`, so their instantiations are what
+// they were. Any other Q (k_shade's pool form, rt_shade.hpp: a caller-supplied ray) brings its own LDS slots (q.pb /
+// q.hid: this lane's level-0 slots; q.tq: the wave's queue when Q::TQ), its levels' closest hits
+// (q.closest_at(it, o, d, best, nd)) and what it keeps of them (q.out(it, orig, best)); A is then any struct with s,
+// bounces and regroup. The shading arithmetic exists once.
+struct FramePath {
+    static constexpr bool TQ = true;
+};
+template <int MAXB, bool COUNT, class ARGS = KArgs, class Q = FramePath>
+__device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3 d, int* __restrict__ stk, Ctr& c,
+                                             UCtr& u, int hpix, int* __restrict__ sstk, int wcap, const Q& q = Q()) {
+    constexpr bool FRAME = std::is_same<Q, FramePath>::value;
+    float4 *pb, *pbw;
+    int *hid, *tq;
+    if constexpr (FRAME) {
+        extern __shared__ int lds_dyn[];
+        float4* pb0 = (float4*)(lds_dyn + wstack_words(wcap, true) * BLOCK);
+        const size_t wl = (size_t)((threadIdx.x >> 6) * MAXB) * 64 + (threadIdx.x & 63);
+        pb = pb0 + wl;
+        pbw = pb - (threadIdx.x & 63);  // the wave's slots of level 0
+        hid = (int*)(pb0 + (size_t)BLOCK * MAXB) + wl;
+        // the wave's packed-triangle queue (TQ_*): the closest walks' result slots empty, its counter 0
+        tq = (int*)(pb0 + (size_t)BLOCK * MAXB) + BLOCK * MAXB + (threadIdx.x >> 6) * TQ_WORDS;
+        tq_clear(tq);
+    } else {
+        pb = q.pb;
+        pbw = pb - (threadIdx.x & 63);
+        hid = q.hid;
+        tq = q.tq;
+    }
     const DScene& s = A.s;
     const v3 amb = mk(s.amb_x, s.amb_y, s.amb_z);
     const v3 d0 = d;
@@ -437,15 +456,20 @@ __device__ __forceinline__ v3 trace_path_dfr(const KArgs& A, bool alive, v3 o, v
         if (alive) {
             float best;
             int nd;
-            const int orig =
-                closest<false, COUNT, true, false, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
-            if (hpix >= 0) {
-                const int h = opaque(hpix);  // (the outputs' addresses formed here, not hoisted and held: OPAQUE_OUT)
-                if (it == 0) {
-                    if (A.hit) A.hit[h] = orig;
-                    if (A.t) A.t[h] = best;
+            int orig;
+            if constexpr (FRAME) {
+                orig = closest<false, COUNT, true, false, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
+                if (hpix >= 0) {
+                    const int h = opaque(hpix);  // (the outputs' addresses formed here, not hoisted and held: OPAQUE_OUT)
+                    if (it == 0) {
+                        if (A.hit) A.hit[h] = orig;
+                        if (A.t) A.t[h] = best;
+                    }
+                    if (A.bounce_hit) A.bounce_hit[(size_t)h * A.bounces + it] = orig;
                 }
-                if (A.bounce_hit) A.bounce_hit[(size_t)h * A.bounces + it] = orig;
+            } else {
+                orig = q.closest_at(it, o, d, best, nd);
+                q.out(it, orig, best);
             }
             if (orig < 0) {  // raytracer.c:132-135 (the colour is written by the shading loop below)
                 hid[it * 64] = -1;
@@ -490,8 +514,8 @@ __device__ __forceinline__ v3 trace_path_dfr(const KArgs& A, bool alive, v3 o, v
     if (nhits) {  // every level's shadow rays as one pool
         u.skip += nhits * (unsigned)s.n_lights;
         const unsigned sh0 = u.shad;
-        shadow_pool<COUNT, MAXB, true>(s, [&](int l) { return (unsigned)(okm >> (8 * l)) & 0xFFu; }, pbw, stk, sstk, wcap,
-                                       A.regroup, c, u, tq);
+        shadow_pool<COUNT, MAXB, Q::TQ>(s, [&](int l) { return (unsigned)(okm >> (8 * l)) & 0xFFu; }, pbw, stk, sstk, wcap,
+                                        A.regroup, c, u, tq);
         u.skip -= u.shad - sh0;
     }
     v3 dl = d0;  // level i's direction: the primary one, then each level's reflection

@@ -117,6 +117,24 @@ class QueryInfo(ctypes.Structure):  # rt_query_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+class Shade(ctypes.Structure):  # rt_shade
+    _fields_ = [("origin", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("bounces", ctypes.c_int), ("kernel", ctypes.c_int), ("regroup", ctypes.c_int),
+                ("unclamped", ctypes.c_int)]
+
+
+class ShadeResults(ctypes.Structure):  # rt_shade_results
+    _fields_ = [("rgb", ctypes.c_void_p), ("bgra", ctypes.c_void_p), ("hit", ctypes.c_void_p),
+                ("t", ctypes.c_void_p), ("bounce_hit", ctypes.c_void_p)]
+
+
+class ShadeInfo(ctypes.Structure):  # rt_shade_info
+    _fields_ = [("rays", ctypes.c_longlong), ("hits", ctypes.c_longlong), ("reflection", ctypes.c_longlong),
+                ("shadow", ctypes.c_longlong), ("shadow_skipped", ctypes.c_longlong),
+                ("strict_paths", ctypes.c_longlong), ("tie_rewalks", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 _host = None
 _hip = None
 
@@ -201,6 +219,8 @@ def hip():
         L.rt_comm_destroy.restype = None
         L.rt_trace_rays.argtypes = [ctypes.c_void_p, P(Rays), P(RayResults)]
         L.rt_get_query_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
+        L.rt_shade_rays.argtypes = [ctypes.c_void_p, P(Shade), P(ShadeResults)]
+        L.rt_get_shade_info.argtypes = [ctypes.c_void_p, P(ShadeInfo)]
         L.rt_device_count.argtypes = []
         L.rt_version.restype = ctypes.c_char_p
         _hip = L

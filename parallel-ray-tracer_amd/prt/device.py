@@ -406,6 +406,39 @@ class Renderer:
         self._chk(_L.rt_get_query_info(self._ctx, ctypes.byref(i)), "rt_get_query_info")
         return {f: getattr(i, f) for f, _ in _lib.QueryInfo._fields_}
 
+    def shade_rays(self, origins, dirs, bounces=4, kernel="auto", regroup=0, unclamped=False, rgb=None, bgra=None,
+                   hit=None, t=None, bounce_hit=None):
+        """rt_shade_rays: the colour the reference's raytrace() gives each ray o + t d (shading, shadow rays, the
+        reflection chain of `bounces` levels; bit-exact) -> rgb [n, 3] float32, clamped to [0, 1] like a frame's pixel
+        (unclamped=True: raytrace()'s value as is). Rays as trace_rays takes them (prt.rays makes some). Optional
+        outputs: bgra [n] int32 (the BMP-quantised pixel; not with unclamped), hit [n] int32 and t [n] float32 (the
+        level-0 closest hit, trace_rays' answer), bounce_hit [n, bounces] int32. rgb is allocated when no output is
+        given, and returned (None when other outputs were given without it). regroup (fast kernel): the shadow pool's
+        refill threshold in idle lanes, 64 = the lockstep form, 0 = the library's choice; the answer does not depend
+        on it. Asynchronous on the renderer's stream: sync() or shade_info() before reading on another stream."""
+        import torch
+        if unclamped and bgra is not None:
+            raise RtError("shade_rays: unclamped has no bgra quantisation")
+        po, pd, n = self._rays(origins, dirs)
+        if rgb is None and bgra is None and hit is None and t is None and bounce_hit is None:
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=f"cuda:{self.device}")
+        i32 = (torch.int32,)
+        res = _lib.ShadeResults(_ptr(rgb, "rgb", 3 * n, (torch.float32,), self.device),
+                                _ptr(bgra, "bgra", n, (torch.int32, getattr(torch, "uint32", torch.int32)), self.device),
+                                _ptr(hit, "hit", n, i32, self.device), _ptr(t, "t", n, (torch.float32,), self.device),
+                                _ptr(bounce_hit, "bounce_hit", n * bounces, i32, self.device))
+        q = _lib.Shade(po, pd, n, bounces, KERNELS.get(kernel, kernel), regroup, 1 if unclamped else 0)
+        self._chk(_L.rt_shade_rays(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_shade_rays")
+        return rgb
+
+    def shade_info(self):
+        """rt_get_shade_info: the last shade query's counters (rays, hits, reflection, shadow, shadow_skipped as
+        stats() counts a frame's; strict_paths outside the fast walks' domain; tie_rewalks) and kernel_ms;
+        synchronises; raises when the query overflowed a stack"""
+        i = _lib.ShadeInfo()
+        self._chk(_L.rt_get_shade_info(self._ctx, ctypes.byref(i)), "rt_get_shade_info")
+        return {f: getattr(i, f) for f, _ in _lib.ShadeInfo._fields_}
+
     def stats(self):
         s = Stats()
         self._chk(_L.rt_get_stats(self._ctx, ctypes.byref(s)), "rt_get_stats")

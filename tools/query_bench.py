@@ -11,7 +11,9 @@ query's counters and the library's md5. Ray sets, each W x H rays:
   window_occluded / window_occluded_perm       the same with every direction inside that window (in_window)
 and, for context beside primary_rows, the frame kernel's own rate (stats()["rays"] / kernel_ms of a `persist` frame).
 The fast and the strict kernel answer with the same bits (checked here on every set).
-usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]"""
+--mode shade times rt_shade_rays instead (shade_mode below).
+usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
+       python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]"""
 import argparse
 import json
 import os
@@ -28,12 +30,17 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--mode", choices=["trace", "shade"], default="trace",
+                    help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode)")
+    ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
     import torch
     from prt import device, host
     W, H = a.width, a.height
     md5 = device.lib_md5()
+    if a.mode == "shade":
+        return shade_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -97,6 +104,77 @@ def main():
                     fm.append(r.sync())
                 line["frame_persist_mrays_s"] = round(r.stats()["rays"] / statistics.median(fm) / 1e3, 1)
             print(json.dumps(line), flush=True)
+        r.close()
+
+
+def shade_mode(a, md5):
+    """--mode shade: per scene, the W x H camera's rays through rt_shade_rays in row-major order and in
+    a fixed random permutation, on the lockstep form (regroup 64) and the pool form at --regroups (and, for context, in
+    8x8-tile order on the lockstep form and the pool at 16, and row-major with regroup 0, the default), and beside them
+    rt_render of the same camera (variant persist, and the default rule once its shape is settled): the project's
+    existing way to shade those rays, on the same build. One untimed round first (and the default rule's trial
+    frames); then --runs rounds with the arms interleaved; kernel_ms from the HIP events around each launch. One JSON
+    line per arm: median / min / max ms, the query's counters, whether its rgb equals the strict-checked render's."""
+    import torch
+    from prt import device, host, rays
+    W, H, n = a.width, a.height, a.width * a.height
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        cam = host.camera(W, H)
+        o, d = rays.pinhole(cam, W, H)
+        perm = torch.randperm(n, generator=torch.Generator(device="cpu").manual_seed(1)).cuda()
+        po, pd = o[perm].contiguous(), d[perm].contiguous()
+        frame = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        out = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        r.render(cam, W, H, kernel="strict", rgb=frame)
+        r.sync()
+        want = {"rows": frame.reshape(n, 3).clone()}
+        want["perm"] = want["rows"][perm].contiguous()
+        # (context: the same rays in 8x8-tile order, a wave's 64 rays one tile as the frame kernels deal them)
+        idx = torch.arange(n).reshape(H, W)
+        tiles = torch.cat([idx[y:y + 8, x:x + 8].reshape(-1) for y in range(0, H, 8) for x in range(0, W, 8)]).cuda()
+        want["tiles"] = want["rows"][tiles].contiguous()
+        sets = {"rows": (o, d), "perm": (po, pd), "tiles": (o[tiles].contiguous(), d[tiles].contiguous())}
+
+        def shade(order, regroup):
+            so, sd = sets[order]
+            r.shade_rays(so, sd, regroup=regroup, rgb=out)
+            info = r.shade_info()
+            torch.cuda.synchronize()
+            return info, bool((out.view(torch.int32) == want[order].view(torch.int32)).all())
+
+        def render(variant):
+            r.render(cam, W, H, kernel="fast", variant=variant, rgb=frame)
+            ms = r.sync()
+            return {"kernel_ms": ms, "variant_ran": r.launch_info()["variant"]}, \
+                bool((frame.reshape(n, 3).view(torch.int32) == want["rows"].view(torch.int32)).all())
+
+        arms = [(f"shade_{order}_{'lockstep' if rg == 64 else 'pool%d' % rg}", (lambda order=order, rg=rg: shade(order, rg)))
+                for order in ("rows", "perm") for rg in [64] + list(a.regroups)]
+        arms += [("shade_tiles_lockstep", lambda: shade("tiles", 64)),
+                 ("shade_tiles_pool16", lambda: shade("tiles", 16)), ("shade_rows_default", lambda: shade("rows", 0)),
+                 ("render_persist", lambda: render("persist")), ("render_default", lambda: render("default"))]
+        for _ in range(64):  # the default rule's trial frames of this shape
+            render("default")
+            if r.launch_info()["settled"]:
+                break
+        for _, fn in arms:
+            fn()
+        ms, last, same = {k: [] for k, _ in arms}, {}, {k: True for k, _ in arms}
+        for _ in range(a.runs):
+            for k, fn in arms:
+                last[k], eq = fn()
+                ms[k].append(last[k]["kernel_ms"])
+                same[k] = same[k] and eq
+        for k, _ in arms:
+            med = statistics.median(ms[k])
+            print(json.dumps({"scene": name, "arm": k, "rays": n, "width": W, "height": H,
+                              "kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms[k]), 4),
+                              "kernel_ms_max": round(max(ms[k]), 4), "runs": a.runs, "equals_strict_render": same[k],
+                              "info": {x: v for x, v in last[k].items() if x != "kernel_ms"}, "lib_md5": md5}),
+                  flush=True)
         r.close()
 
 
