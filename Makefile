@@ -28,7 +28,9 @@ cli: $(BIN)/raytracer
 
 HOST_SRCS := $(CSRC)/host/rt_host.cpp $(CSRC)/host/rt_wide.cpp $(CSRC)/host/rt_cache.cpp
 
-$(LIB)/librt_host.so: $(HOST_SRCS) include/rt_host.h include/rt_types.h
+HOST_HDRS := include/rt_host.h include/rt_types.h $(CSRC)/hip/rt_quant.hpp
+
+$(LIB)/librt_host.so: $(HOST_SRCS) $(HOST_HDRS)
 	@mkdir -p $(LIB)
 	g++ $(HOST_FLAGS) -shared -o $@ $(HOST_SRCS)
 
@@ -65,7 +67,7 @@ $(RCP_CHECK): tools/rcp/rcp_exhaustive.hip $(CSRC)/hip/rt_device.hpp
 # must come first). Build container only (CPU; no GPU code is involved).
 ASAN_DIR   := build/asan
 ASAN_FLAGS := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all
-$(ASAN_DIR)/librt_host.so: $(HOST_SRCS) include/rt_host.h include/rt_types.h
+$(ASAN_DIR)/librt_host.so: $(HOST_SRCS) $(HOST_HDRS)
 	@mkdir -p $(ASAN_DIR)
 	g++ $(HOST_FLAGS) $(ASAN_FLAGS) -shared -o $@ $(HOST_SRCS)
 

@@ -363,6 +363,57 @@ typedef struct rt_shade_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info);
 
+/* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
+ * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
+ * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.
+ *
+ * The contract: after rt_update_vertices every render, ray query and radiance query, strict kernel and every fast
+ * variant, gives the bits a fresh rt_upload_scene of the scene S' gives, where
+ *   triangles[i] = triangle_init(coords'[i], ks_i, kd_i, kr_i): materials kept, centroid and norm[0], norm[1]
+ *                  recomputed exactly as cpu/src/triangle.c:14-19 computes them;
+ *   bvh          = the uploaded reference tree with the same child, tr_len and tri_idx, every node's min / max regrown
+ *                  as cpu/src/bvh.c grows it: aabb_grow over the node's triangles' vertices starting from +-1e10 (an
+ *                  empty node keeps +-1e10);
+ *   lights, ambient and accel mode unchanged.
+ * What an update is not: a new bvh_build of the moved triangles, whose topology can differ from the kept one. That
+ * difference shows only at exact ties (the first-found rule follows the tree's order).
+ * The fast views keep their topology too, which can only cost speed (rt_update_info.area_ratio says how loose the
+ * full view's boxes have become); a subset view (unit, primary) that newly hittable triangles must join cannot be
+ * refitted and is rebuilt through the upload's own path, on the host (views_rebuilt; a triangle that stops being
+ * hittable simply stays in its view). rt_scene_info's view fields follow what the update did.
+ * The default rule's per-shape launch decisions survive an update (an animation does not re-trial every frame); the
+ * query and shade state is untouched; the inflation 2^-16 x magnitude and the queries' origin bound follow the new
+ * coordinates.
+ * Errors: RT_E_STATE before an upload; RT_E_ARG for a null pointer, a count mismatch or a non-finite coordinate --
+ * found by a read-only first pass, so a refused update leaves the scene exactly as it was.
+ * coords is read in stream order on the context stream. The call waits on the host once, for that first pass's few
+ * words (and, the first time after an upload or a rebuild, before that pass, for the trees' level lists and the face
+ * lists' buffers); everything after is asynchronous, except a view's rebuild. */
+typedef struct rt_vertex_update {
+    const float* coords;  /* device, [n_triangles][3][3] f32: the new triangle_t.coords of every triangle, original order */
+    int n_triangles;      /* must equal the uploaded scene's */
+} rt_vertex_update;
+int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u);
+
+typedef struct rt_update_info {
+    int views_refit, views_rebuilt;   /* wide views (full / unit / primary) refitted in place / rebuilt because membership changed */
+    int joined_unit, joined_primary;  /* triangles that became hittable for a view they were absent from (what forces a rebuild) */
+    float scene_magnitude;            /* the new scene's, as the boxes' inflation uses it */
+    float area_ratio;                 /* full view: summed surface area of all decoded child boxes now / when the view was last built (1 without a wide view) */
+    float update_ms;                  /* HIP events around the whole update on the context stream */
+} rt_update_info;
+/* of the last update (synchronises); RT_E_STATE before the first update */
+int rt_get_update_info(rt_ctx* ctx, rt_update_info* info);
+
+/* New light positions and colours: a stream-ordered copy (host array; n_lights must equal the scene's) */
+int rt_update_lights(rt_ctx* ctx, const rt_light* lights, int n_lights);
+
+/* Test-only read-back of a wide view as it stands on the device (synchronises): view 0 = full, 1 = unit, 2 = primary.
+ * Returns the view's node count (0: no such view) or < 0; copies min(count, cap_nodes) nodes of 20 words into nodes and
+ * min(triangles, cap_tris) entries of the view's position -> original triangle map into tri_orig (both nullable).
+ * tests/test_gpu_refit.py compares the words with rth_wbvh_refit's. Not part of the supported interface. */
+int rt_debug_read_wide(rt_ctx* ctx, int view, unsigned int* nodes, int cap_nodes, int* tri_orig, int cap_tris);
+
 /* load_from_gpu(): copies the last frame's compact rows to host (synchronous); nullable args. RT_E_KERNEL when the
  * render reported a traversal-stack overflow (its frame is not valid). */
 int rt_download(rt_ctx* ctx, float* h_rgb, int* h_hit);

@@ -81,6 +81,15 @@ int rth_wbvh_build(const rt_bvh_node* bvh, int n_nodes, const int* tri_idx, cons
 int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const int* tri_idx, const rt_triangle* tris, int n_tris,
                         float inflate, float c_node, uint32_t** nodes, int** tri_order, rth_wbvh_info* info);
 
+/* Refit: the boxes of a built wide tree for moved triangles, in place. nodes / tri_order as rth_wbvh_build returned
+ * them, tris the same triangles at their new coordinates (only coords is read). Bottom-up, every node's occupied
+ * slots get their subtree's exact box grown by `inflate` and are re-quantised outward by the collapse's rule
+ * (rt_quant.hpp); the origin, the exponents and the plane words are rewritten, every topology word (imask,
+ * child_base, tri_base, meta, the slot assignment) stays. With unmoved triangles it reproduces rth_wbvh_build's
+ * words. The device refit (rt_update_vertices) runs the same code per node and is checked against this one. */
+int rth_wbvh_refit(uint32_t* nodes, int n_nodes, const int* tri_order, const rt_triangle* tris, int n_tris,
+                   float inflate);
+
 /* ---- camera: cam_init + cam.rot.x + cam_calculate_screen_coords + inc_x/inc_y
  * (cpu/src/cam.c:5-48, main.c:105-106, main.c:243-250) for a width x height frame:
  * pos (0,-9,3), fov pi/3.2, rot.x = -pi/12. */

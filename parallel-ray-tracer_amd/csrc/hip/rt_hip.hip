@@ -33,6 +33,7 @@
 #include "rt_feedback.hpp"
 #include "rt_query.hpp"
 #include "rt_shade.hpp"
+#include "rt_refit.hpp"
 #ifndef PRT_TREELET
 #define PRT_TREELET 2  // treelet-restructuring passes over the GPU-built binary tree (0: none)
 #endif
@@ -85,6 +86,18 @@ struct DevWide {
     rtd::DWide view() const { return rtd::DWide{nodes, tris, orig, n}; }
 };
 
+// What a refit (rt_update_vertices) keeps per topology, made at the first update after the view was built.
+// A binary view: its records by tree level (d_list: all records, level l at [off[l], off[l + 1]), root level first).
+// A wide view: its levels as ranges of the breadth-first node array (off), and the bitmap of the triangles it holds.
+// Both: the scratch array of exact boxes (two float4 per record / node).
+struct RefitTopo {
+    bool made = false;
+    std::vector<int> off;
+    int* d_list = nullptr;
+    unsigned* d_bits = nullptr;
+    float4* d_exact = nullptr;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -106,9 +119,8 @@ struct rt_ctx {
     // view), packed triangle-test jobs a 26-bit triangle (rtd::TQ_MAX_TRIS); larger scenes run the unpacked builds
     bool pk_ok = true, tq_ok = true;
     float amb[3] = {0.5f, 0.5f, 0.5f};
-    // every face coordinate of the reference tree's child boxes, per axis, sorted; on the device one after another
-    // (rtd::DScene::faces)
-    std::vector<float> faces[3];
+    // every face coordinate of the reference tree's child boxes, per axis, sorted, one axis after another
+    // (rtd::DScene::faces; n_face below)
     float* d_faces = nullptr;
     bool has_scene = false;
     rt_scene_info info{};  // what the last upload built (rt_get_scene_info)
@@ -171,6 +183,26 @@ struct rt_ctx {
     long long scene_gen = 0;  // bumped by every upload
     // ray queries (rt_trace_rays, rt_query.hpp): their own counter block ([rtd::Q_NCOUNT] counters, then the chunk
     // counter) and event pair -- nothing a render call owns is touched
+    // vertex updates (rt_update_vertices, rt_refit.hpp): what the upload built and how (a view's rebuild repeats it),
+    // the per-topology refit data of the five views, the plan pass's words, the face lists' sort buffers
+    int built_accel = 0, ploc_radius = 0;
+    float collapse_cost = 0.0f;
+    int n_face[3] = {0, 0, 0};  // rtd::DScene::n_face (the upload's distinct faces; after an update all 4 per record)
+    RefitTopo tp_ref, tp_acc, tp_wide, tp_unit, tp_prim;
+    unsigned* d_plan = nullptr;  // [rtr::P_WORDS]
+    unsigned* h_plan = nullptr;  // pinned
+    double* d_area = nullptr;    // [2]: the full view's decoded child-box area when it was built, and now
+    bool area_base = false;      // d_area[0] holds the current build's
+    float* d_face_tmp = nullptr; // unsorted faces [3][4 records]
+    void* d_sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    bool faces_own = false;      // d_faces has room for every record's faces (set by the first update)
+    hipEvent_t u_ev0 = nullptr, u_ev1 = nullptr;  // around the last update made
+    hipEvent_t u_evs = nullptr;                   // the start of the update under way (u_ev0 once it is made)
+    bool updated = false;
+    rt_update_info uinfo{};
+    float4* h_lights = nullptr;  // pinned staging of rt_update_lights, 2 x n_lights (freed with the scene)
+    hipEvent_t lights_ev = nullptr;
     float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
     unsigned long long* d_query = nullptr;
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
@@ -281,14 +313,34 @@ void free_wide(DevWide& w) {
     w = DevWide();
 }
 
+void free_topo(RefitTopo& t) {
+    for (void* p : {(void*)t.d_list, (void*)t.d_bits, (void*)t.d_exact})
+        if (p) (void)hipFree(p);
+    t = RefitTopo();
+}
+
 void free_scene(rt_ctx* ctx) {
+    for (RefitTopo* t : {&ctx->tp_ref, &ctx->tp_acc, &ctx->tp_wide, &ctx->tp_unit, &ctx->tp_prim}) free_topo(*t);
+    for (void* p : {(void*)ctx->d_face_tmp, ctx->d_sort_tmp})
+        if (p) (void)hipFree(p);
+    ctx->d_face_tmp = nullptr;
+    ctx->d_sort_tmp = nullptr;
+    ctx->sort_bytes = 0;
+    ctx->faces_own = false;
+    ctx->area_base = false;
+    ctx->updated = false;
+    if (ctx->h_lights) {  // rt_update_lights' staging is sized for this scene's lights (its last copy has run first)
+        if (ctx->lights_ev) (void)hipEventSynchronize(ctx->lights_ev);
+        (void)hipHostFree(ctx->h_lights);
+        ctx->h_lights = nullptr;
+    }
     free_view(ctx->ref);
     free_view(ctx->acc);
     for (DevWide* w : {&ctx->wide, &ctx->unit, &ctx->prim}) free_wide(*w);
     for (void* p : {(void*)ctx->d_shade, (void*)ctx->d_mats, (void*)ctx->d_lights, (void*)ctx->d_faces})
         if (p) (void)hipFree(p);
     ctx->d_faces = nullptr;
-    for (auto& f : ctx->faces) f.clear();
+    for (int& f : ctx->n_face) f = 0;
     ctx->d_shade = nullptr;
     ctx->d_mats = nullptr;
     ctx->d_lights = nullptr;
@@ -912,7 +964,10 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
         free_scene(ctx);
         return rc;
     }
-    for (int a = 0; a < 3; a++) ctx->faces[a].swap(faces[a]);
+    for (int a = 0; a < 3; a++) ctx->n_face[a] = (int)faces[a].size();
+    ctx->built_accel = built;
+    ctx->ploc_radius = sc->ploc_radius;
+    ctx->collapse_cost = sc->collapse_node_cost;
     ctx->n_lights = sc->n_lights;
     ctx->n_tris = n;
     ctx->pk_ok = std::max(ctx->wide.n, std::max(ctx->unit.n, ctx->prim.n)) <= rtd::WIDE_MAX_NODES &&
@@ -1147,7 +1202,7 @@ rtd::DScene scene_args(const rt_ctx* ctx) {
     s.faces = ctx->d_faces;  // (rt_kernels.hpp degenerate_ok)
     s.ref_path = ctx->ref.path;  // (rt_kernels.hpp ref_reaches)
     s.n_tris = ctx->n_tris;
-    for (int a = 0; a < 3; a++) s.n_face[a] = (int)ctx->faces[a].size();
+    for (int a = 0; a < 3; a++) s.n_face[a] = ctx->n_face[a];
     return s;
 }
 
@@ -2094,6 +2149,350 @@ extern "C" int rt_get_query_info(rt_ctx* ctx, rt_query_info* info) {
         return RT_E_KERNEL;
     }
     return RT_OK;
+}
+
+// ---------------------------------------------------------------- vertex updates (rt_refit.hpp)
+namespace {
+
+// the smallest double x whose square root reaches thr: sqrt is correctly rounded, hence monotonic, so hittable()'s
+// sqrt(len2) >= thr is len2 >= x, which the plan kernel evaluates without a device square root
+double sqrt_threshold(double thr) {
+    double x = thr * thr;
+    while (x > 0.0 && std::sqrt(x) >= thr) x = std::nextafter(x, 0.0);
+    while (std::sqrt(x) < thr) x = std::nextafter(x, (double)INFINITY);
+    return x;
+}
+
+// A binary view's records by tree level, from the device's own records (a record's parent is its 4th float4's z and
+// precedes it: build_view numbers the records in preorder). Once per topology; waits for the stream.
+int make_bin_topo(rt_ctx* ctx, const DevView& v, RefitTopo& t) {
+    if (t.made) return RT_OK;
+    const int n = v.n_inner;
+    std::vector<float4> h(4 * (size_t)n);
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (n) HIPC(hipMemcpy(h.data(), v.nodes, sizeof(float4) * h.size(), hipMemcpyDeviceToHost));
+    std::vector<int> depth(n, 0);
+    int levels = 0;
+    for (int r = 0; r < n; r++) {
+        int par;
+        std::memcpy(&par, &h[4 * (size_t)r + 3].z, 4);
+        if (par >= r) {
+            ctx->err = "rt_update_vertices: a binary view's records are not in preorder";
+            return RT_E_STATE;
+        }
+        depth[r] = par < 0 ? 0 : depth[par] + 1;
+        levels = std::max(levels, depth[r] + 1);
+    }
+    t.off.assign((size_t)levels + 1, 0);
+    for (int r = 0; r < n; r++) t.off[(size_t)depth[r] + 1]++;
+    for (int l = 0; l < levels; l++) t.off[(size_t)l + 1] += t.off[l];
+    std::vector<int> list(std::max(n, 1)), at(t.off.begin(), t.off.end());
+    for (int r = 0; r < n; r++) list[at[depth[r]]++] = r;
+    HIPC(hipMalloc((void**)&t.d_list, sizeof(int) * list.size()));
+    HIPC(hipMemcpy(t.d_list, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
+    HIPC(hipMalloc((void**)&t.d_exact, sizeof(float4) * 2 * (size_t)std::max(n, 1)));
+    t.made = true;
+    return RT_OK;
+}
+
+// A wide view's levels: the collapse lays the nodes out breadth first, every level one range whose interior slots'
+// children, in node and slot order, are the next range (rt_wide.cpp) -- checked here. bitmap: also the set of the
+// triangles the view holds (a subset view's membership). Once per topology; waits for the stream.
+int make_wide_topo(rt_ctx* ctx, const DevWide& w, RefitTopo& t, bool bitmap) {
+    if (t.made) return RT_OK;
+    const int n = w.n;
+    std::vector<uint32_t> h(20 * (size_t)n);
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMemcpy(h.data(), w.nodes, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost));
+    t.off = {0, 1};
+    for (;;) {
+        const int s = t.off[t.off.size() - 2], e = t.off.back();
+        long long next = e;
+        for (int k = s; k < e; k++) {
+            const uint32_t* W = &h[20 * (size_t)k];
+            const int kids = __builtin_popcount(W[3] >> 24);
+            if (kids && (long long)W[4] != next) {
+                ctx->err = "rt_update_vertices: a wide view's nodes are not in breadth-first order";
+                return RT_E_STATE;
+            }
+            next += kids;
+        }
+        if (next == e) break;
+        if (next > n) {
+            ctx->err = "rt_update_vertices: a wide view's child index is out of range";
+            return RT_E_STATE;
+        }
+        t.off.push_back((int)next);
+    }
+    if (t.off.back() != n) {
+        ctx->err = "rt_update_vertices: a wide view has unreachable nodes";
+        return RT_E_STATE;
+    }
+    HIPC(hipMalloc((void**)&t.d_exact, sizeof(float4) * 2 * (size_t)n));
+    if (bitmap) {
+        const size_t words = ((size_t)ctx->n_tris + 31) / 32;
+        HIPC(hipMalloc((void**)&t.d_bits, sizeof(unsigned) * words));
+        HIPC(hipMemsetAsync(t.d_bits, 0, sizeof(unsigned) * words, ctx->stream));
+        rtr::k_member<<<(w.tris_n + 255) / 256, 256, 0, ctx->stream>>>(w.orig, w.tris_n, t.d_bits);
+        HIPC(hipGetLastError());
+    }
+    t.made = true;
+    return RT_OK;
+}
+
+// steps 2-3 for one binary view: its triangle records, then its child boxes level by level, deepest first
+int refit_binary(rt_ctx* ctx, const DevView& v, const RefitTopo& t, const float* coords, float inflate) {
+    hipStream_t st = ctx->stream;
+    rtr::k_tri_records<<<(ctx->n_tris + 255) / 256, 256, 0, st>>>(coords, v.orig, ctx->n_tris, v.tris);
+    for (int l = (int)t.off.size() - 2; l >= 0; l--) {
+        const int cnt = t.off[(size_t)l + 1] - t.off[l];
+        if (cnt <= 0) continue;
+        rtr::k_bin_level<<<(cnt + 255) / 256, 256, 0, st>>>(t.d_list + t.off[l], cnt, v.nodes, v.leaves, v.orig, coords,
+                                                            t.d_exact, inflate);
+    }
+    HIPC(hipGetLastError());
+    return RT_OK;
+}
+
+// steps 2 and 4 for one wide view (area: the full view's decoded-area accumulator, else null)
+int refit_wide(rt_ctx* ctx, const DevWide& w, const RefitTopo& t, const float* coords, float inflate, double* area) {
+    hipStream_t st = ctx->stream;
+    rtr::k_tri_records<<<(w.tris_n + 255) / 256, 256, 0, st>>>(coords, w.orig, w.tris_n, w.tris);
+    for (int l = (int)t.off.size() - 2; l >= 0; l--) {
+        const int first = t.off[l], cnt = t.off[(size_t)l + 1] - first;
+        rtr::k_wide_level<<<(cnt + 63) / 64, 64, 0, st>>>(first, cnt, w.nodes, w.orig, coords, t.d_exact, inflate, area);
+    }
+    HIPC(hipGetLastError());
+    return RT_OK;
+}
+
+// The face lists' buffers, made with the per-topology data (first update after an upload; waits for the stream): the
+// upload's array holds the distinct faces only, a refit writes all four per record. The lists in use move over as
+// they are, so that an update refused after this point leaves the scene as it was.
+int make_face_buffers(rt_ctx* ctx) {
+    const int n = ctx->ref.n_inner;
+    if (ctx->faces_own || n == 0) return RT_OK;
+    const size_t m = 4 * (size_t)n, have = (size_t)ctx->n_face[0] + ctx->n_face[1] + ctx->n_face[2];
+    float* grown = nullptr;
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMalloc((void**)&grown, sizeof(float) * 3 * m));
+    if (ctx->d_faces && have > 0 && have <= 3 * m)
+        HIPC(hipMemcpy(grown, ctx->d_faces, sizeof(float) * have, hipMemcpyDeviceToDevice));
+    if (ctx->d_faces) HIPC(hipFree(ctx->d_faces));
+    ctx->d_faces = grown;
+    HIPC(hipMalloc((void**)&ctx->d_face_tmp, sizeof(float) * 3 * m));
+    HIPC(hipcub::DeviceRadixSort::SortKeys(nullptr, ctx->sort_bytes, ctx->d_face_tmp, ctx->d_faces, (int)m, 0, 32,
+                                           ctx->stream));
+    HIPC(hipMalloc(&ctx->d_sort_tmp, std::max<size_t>(ctx->sort_bytes, 16)));
+    ctx->faces_own = true;
+    return RT_OK;
+}
+
+// step 3's second half: the reference view's face coordinates per axis, sorted on the device (duplicates stay:
+// on_face needs order only)
+int refit_faces(rt_ctx* ctx) {
+    const int n = ctx->ref.n_inner;
+    if (n == 0) {
+        for (int& f : ctx->n_face) f = 0;
+        return RT_OK;
+    }
+    hipStream_t st = ctx->stream;
+    const int m = 4 * n;
+    rtr::k_faces<<<(n + 255) / 256, 256, 0, st>>>(ctx->ref.nodes, n, ctx->d_face_tmp);
+    HIPC(hipGetLastError());
+    for (int a = 0; a < 3; a++) {
+        size_t bytes = ctx->sort_bytes;
+        HIPC(hipcub::DeviceRadixSort::SortKeys(ctx->d_sort_tmp, bytes, ctx->d_face_tmp + (size_t)a * m,
+                                               ctx->d_faces + (size_t)a * m, m, 0, 32, st));
+        ctx->n_face[a] = m;
+    }
+    return RT_OK;
+}
+
+// step 5: a subset view whose membership changed, rebuilt through the upload's own path (subset_view) over the new
+// triangles; none where the new subset is empty or leaves out too little (the full view then serves)
+int rebuild_subset(rt_ctx* ctx, const rt_scene* s2, double dmax, size_t fewer_than, float inflate, DevWide& d,
+                   RefitTopo& t) {
+    HostWide hw;
+    int rc = subset_view(ctx, s2, dmax, fewer_than, ctx->built_accel, inflate, hw);
+    if (rc) return rc;
+    HIPC(hipStreamSynchronize(ctx->stream));
+    free_wide(d);
+    free_topo(t);
+    return upload_wide(ctx, hw, d);
+}
+
+}  // namespace
+
+extern "C" int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_update_vertices: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!u || !u->coords) return arg_err(ctx, "rt_update_vertices: null update / coords");
+    if (u->n_triangles != ctx->n_tris) return arg_err(ctx, "rt_update_vertices: n_triangles differs from the uploaded scene's");
+    HIPC(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int n = ctx->n_tris;
+    const float* coords = u->coords;
+    if (!ctx->d_plan) HIPC(hipMalloc((void**)&ctx->d_plan, sizeof(unsigned) * rtr::P_WORDS));
+    if (!ctx->d_area) HIPC(hipMalloc((void**)&ctx->d_area, sizeof(double) * 2));
+    if (!ctx->h_plan) HIPC(hipHostMalloc((void**)&ctx->h_plan, sizeof(unsigned) * rtr::P_WORDS, hipHostMallocDefault));
+    if (!ctx->u_ev0) HIPC(hipEventCreate(&ctx->u_ev0));
+    if (!ctx->u_ev1) HIPC(hipEventCreate(&ctx->u_ev1));
+    if (!ctx->u_evs) HIPC(hipEventCreate(&ctx->u_evs));
+    // the per-topology data (first update after an upload or a rebuild)
+    int rc;
+    if ((rc = make_bin_topo(ctx, ctx->ref, ctx->tp_ref))) return rc;
+    if (ctx->acc.nodes && (rc = make_bin_topo(ctx, ctx->acc, ctx->tp_acc))) return rc;
+    if (ctx->wide.nodes && (rc = make_wide_topo(ctx, ctx->wide, ctx->tp_wide, false))) return rc;
+    if (ctx->unit.nodes && (rc = make_wide_topo(ctx, ctx->unit, ctx->tp_unit, true))) return rc;
+    if (ctx->prim.nodes && (rc = make_wide_topo(ctx, ctx->prim, ctx->tp_prim, true))) return rc;
+    if ((rc = make_face_buffers(ctx))) return rc;
+    // (the start event becomes u_ev0 only when the update is made: a refused one leaves the last update's pair alone)
+    HIPC(hipEventRecord(ctx->u_evs, st));
+    // 1. the plan pass (read-only), and the one host wait
+    const float floor16 = 16.0f;
+    unsigned init[rtr::P_WORDS] = {0, 0, 0, 0};
+    std::memcpy(&init[rtr::P_MX], &floor16, 4);
+    std::memcpy(ctx->h_plan, init, sizeof init);
+    HIPC(hipMemcpyAsync(ctx->d_plan, ctx->h_plan, sizeof init, hipMemcpyHostToDevice, st));
+    const double x_unit = sqrt_threshold(UNIT_KEEP * (double)rtd::EPS / 1.0);
+    const double x_prim = sqrt_threshold(UNIT_KEEP * (double)rtd::EPS / PRIMARY_D);
+    rtr::k_plan<<<(n + 255) / 256, 256, 0, st>>>(coords, n, ctx->tp_unit.d_bits, ctx->tp_prim.d_bits, x_unit, x_prim,
+                                                 ctx->d_plan);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(ctx->h_plan, ctx->d_plan, sizeof init, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (ctx->h_plan[rtr::P_BAD]) return arg_err(ctx, "rt_update_vertices: a coordinate is not finite (nothing was changed)");
+    float scene_mx;
+    std::memcpy(&scene_mx, &ctx->h_plan[rtr::P_MX], 4);
+    const float inflate = std::ldexp(scene_mx, -16);
+    rt_update_info ui{};
+    ui.joined_unit = (int)ctx->h_plan[rtr::P_JOIN_UNIT];
+    ui.joined_primary = (int)ctx->h_plan[rtr::P_JOIN_PRIM];
+    ui.scene_magnitude = scene_mx;
+    ui.area_ratio = 1.0f;
+    // 5. views that triangles joined: the slow path, on the host
+    const bool re_unit = ctx->unit.nodes && ui.joined_unit > 0, re_prim = ctx->prim.nodes && ui.joined_primary > 0;
+    if (re_unit || re_prim) {
+        std::vector<float> hv(9 * (size_t)n);
+        HIPC(hipMemcpy(hv.data(), coords, sizeof(float) * hv.size(), hipMemcpyDeviceToHost));
+        std::vector<rt_triangle> T((size_t)n);
+        const rt_vec3 zero{0.0f, 0.0f, 0.0f};
+        for (int i = 0; i < n; i++) {  // (the builds read coords and centroid)
+            const float* p = &hv[9 * (size_t)i];
+            const rt_vec3 a{p[0], p[1], p[2]}, b{p[3], p[4], p[5]}, c{p[6], p[7], p[8]};
+            rth_triangle_init(&T[i], &a, &b, &c, &zero, &zero, &zero);
+        }
+        rt_scene s2{};
+        s2.triangles = T.data();
+        s2.n_triangles = n;
+        s2.ploc_radius = ctx->ploc_radius;
+        s2.collapse_node_cost = ctx->collapse_cost;
+        if (re_unit && (rc = rebuild_subset(ctx, &s2, 1.0, (size_t)n, inflate, ctx->unit, ctx->tp_unit))) return rc;
+        if (re_prim && (rc = rebuild_subset(ctx, &s2, PRIMARY_D, (size_t)n - (size_t)n / 50, inflate, ctx->prim, ctx->tp_prim)))
+            return rc;
+        ui.views_rebuilt = (int)re_unit + (int)re_prim;
+        ctx->pk_ok = std::max(ctx->wide.n, std::max(ctx->unit.n, ctx->prim.n)) <= rtd::WIDE_MAX_NODES &&
+                     !(ctx->flags & RT_FLAG_UNPACKED_STACK);
+        ctx->info.unit_triangles = ctx->unit.tris_n;
+        ctx->info.unit_nodes = ctx->unit.n;
+        ctx->info.unit_depth = ctx->unit.depth;
+        ctx->info.primary_triangles = ctx->prim.tris_n;
+        ctx->info.primary_nodes = ctx->prim.n;
+    }
+    // 2. the shading normals (the views' triangle records with each view below)
+    rtr::k_shade_normals<<<(n + 255) / 256, 256, 0, st>>>(coords, n, ctx->d_shade);
+    HIPC(hipGetLastError());
+    // 3. the binary trees: the reference tree with its own boxes, the acceleration tree's grown by the inflation
+    if ((rc = refit_binary(ctx, ctx->ref, ctx->tp_ref, coords, 0.0f))) return rc;
+    if (ctx->acc.nodes && (rc = refit_binary(ctx, ctx->acc, ctx->tp_acc, coords, inflate))) return rc;
+    if ((rc = refit_faces(ctx))) return rc;
+    // 4. the wide views not rebuilt above
+    if (ctx->wide.nodes) {
+        if (!ctx->area_base) {  // the denominator: the un-updated nodes of this build
+            HIPC(hipMemsetAsync(ctx->d_area, 0, sizeof(double), st));
+            rtr::k_wide_area<<<(ctx->wide.n + 255) / 256, 256, 0, st>>>(ctx->wide.nodes, ctx->wide.n, ctx->d_area);
+            HIPC(hipGetLastError());
+            ctx->area_base = true;
+        }
+        HIPC(hipMemsetAsync(ctx->d_area + 1, 0, sizeof(double), st));
+        if ((rc = refit_wide(ctx, ctx->wide, ctx->tp_wide, coords, inflate, ctx->d_area + 1))) return rc;
+        ui.views_refit++;
+    }
+    if (ctx->unit.nodes && !re_unit) {
+        if ((rc = refit_wide(ctx, ctx->unit, ctx->tp_unit, coords, inflate, nullptr))) return rc;
+        ui.views_refit++;
+    }
+    if (ctx->prim.nodes && !re_prim) {
+        if ((rc = refit_wide(ctx, ctx->prim, ctx->tp_prim, coords, inflate, nullptr))) return rc;
+        ui.views_refit++;
+    }
+    std::swap(ctx->u_ev0, ctx->u_evs);
+    HIPC(hipEventRecord(ctx->u_ev1, st));
+    ctx->scene_mx = scene_mx;
+    ctx->uinfo = ui;
+    ctx->updated = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_update_info(rt_ctx* ctx, rt_update_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->updated) {
+        ctx->err = "rt_get_update_info: no vertex update made";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    *info = ctx->uinfo;
+    if (ctx->wide.nodes && ctx->area_base) {
+        double a[2] = {0.0, 0.0};
+        HIPC(hipMemcpy(a, ctx->d_area, sizeof a, hipMemcpyDeviceToHost));
+        info->area_ratio = a[0] > 0.0 ? (float)(a[1] / a[0]) : 1.0f;
+    }
+    HIPC(hipEventElapsedTime(&info->update_ms, ctx->u_ev0, ctx->u_ev1));
+    return RT_OK;
+}
+
+extern "C" int rt_update_lights(rt_ctx* ctx, const rt_light* lights, int n_lights) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_update_lights: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (n_lights != ctx->n_lights) return arg_err(ctx, "rt_update_lights: n_lights differs from the uploaded scene's");
+    if (n_lights > 0 && !lights) return arg_err(ctx, "rt_update_lights: null lights");
+    if (n_lights == 0) return RT_OK;
+    HIPC(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(float4) * 2 * (size_t)n_lights;
+    if (!ctx->lights_ev) HIPC(hipEventCreateWithFlags(&ctx->lights_ev, hipEventDisableTiming));
+    else HIPC(hipEventSynchronize(ctx->lights_ev));  // (the staging's previous copy has run)
+    if (!ctx->h_lights) HIPC(hipHostMalloc((void**)&ctx->h_lights, bytes, hipHostMallocDefault));
+    for (int j = 0; j < n_lights; j++) {  // the upload's 32-B layout
+        ctx->h_lights[2 * j] = make_float4(lights[j].pos.x, lights[j].pos.y, lights[j].pos.z, 0.0f);
+        ctx->h_lights[2 * j + 1] = make_float4(lights[j].kl.x, lights[j].kl.y, lights[j].kl.z, 0.0f);
+    }
+    HIPC(hipMemcpyAsync(ctx->d_lights, ctx->h_lights, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipEventRecord(ctx->lights_ev, ctx->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_read_wide(rt_ctx* ctx, int view, unsigned int* nodes, int cap_nodes, int* tri_orig, int cap_tris) {
+    if (!ctx || view < 0 || view > 2 || cap_nodes < 0 || cap_tris < 0) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_debug_read_wide: no scene uploaded";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    const DevWide& w = view == 0 ? ctx->wide : (view == 1 ? ctx->unit : ctx->prim);
+    if (!w.nodes) return 0;
+    const int nn = std::min(w.n, cap_nodes), nt = std::min(w.tris_n, cap_tris);
+    if (nodes && nn > 0) HIPC(hipMemcpy(nodes, w.nodes, sizeof(unsigned) * 20 * (size_t)nn, hipMemcpyDeviceToHost));
+    if (tri_orig && nt > 0) HIPC(hipMemcpy(tri_orig, w.orig, sizeof(int) * (size_t)nt, hipMemcpyDeviceToHost));
+    return w.n;
 }
 
 // ---------------------------------------------------------------- radiance queries (rt_shade.hpp)
@@ -3074,6 +3473,12 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_query) (void)hipFree(ctx->d_query);
     if (ctx->q_ev0) (void)hipEventDestroy(ctx->q_ev0);
     if (ctx->q_ev1) (void)hipEventDestroy(ctx->q_ev1);
+    for (void* p : {(void*)ctx->d_plan, (void*)ctx->d_area})
+        if (p) (void)hipFree(p);
+    if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
+    if (ctx->h_lights) (void)hipHostFree(ctx->h_lights);
+    for (hipEvent_t e : {ctx->u_ev0, ctx->u_ev1, ctx->u_evs, ctx->lights_ev})
+        if (e) (void)hipEventDestroy(e);
     if (ctx->d_shq) (void)hipFree(ctx->d_shq);
     if (ctx->s_ev0) (void)hipEventDestroy(ctx->s_ev0);
     if (ctx->s_ev1) (void)hipEventDestroy(ctx->s_ev1);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "rt_host.h"
+#include "../hip/rt_quant.hpp"  // the quantiser the refit shares with the device (rth_wbvh_refit below)
 
 namespace {
 
@@ -562,6 +563,44 @@ extern "C" int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const in
         info->n_tris = (int)order.size();
         info->depth = depth;
         info->max_children = max_kids;
+    }
+    return RT_OK;
+}
+
+// ---- refit (rt_quant.hpp): the wide tree's boxes for moved triangles, topology kept
+
+extern "C" int rth_wbvh_refit(uint32_t* nodes, int n_nodes, const int* tri_order, const rt_triangle* tris, int n_tris,
+                              float inflate) {
+    if (!nodes || n_nodes <= 0 || !tri_order || !tris || n_tris <= 0 || !(inflate >= 0.0f)) return RT_E_ARG;
+    // children follow their parents (breadth-first layout): one pass from the last node to the root
+    std::vector<rtq::Box> exact((size_t)n_nodes);
+    for (int k = n_nodes - 1; k >= 0; k--) {
+        uint32_t* W = nodes + 20 * (size_t)k;
+        rtq::Box box[rtq::WIDTH];
+        rtq::Box own = rtq::empty_box();
+        for (int s = 0; s < rtq::WIDTH; s++) {
+            if (!rtq::occupied(W, s)) continue;
+            if ((rtq::imask_of(W) >> s) & 1u) {
+                const uint32_t c = rtq::child_of(W, s);
+                if (c <= (uint32_t)k || c >= (uint32_t)n_nodes) return RT_E_ARG;
+                box[s] = exact[c];
+            } else {
+                const uint32_t m = rtq::meta_of(W, s), cnt = m >> 5, off = m & 31u;
+                if ((uint64_t)W[5] + off + cnt > (uint64_t)n_tris) return RT_E_ARG;
+                box[s] = rtq::empty_box();
+                for (uint32_t i = 0; i < cnt; i++) {
+                    const int t = tri_order[W[5] + off + i];
+                    if (t < 0 || t >= n_tris) return RT_E_ARG;
+                    for (const rt_vec3& c : tris[t].coords) {
+                        const float v[3] = {c.x, c.y, c.z};
+                        rtq::grow(box[s], v);
+                    }
+                }
+            }
+            rtq::grow(own, box[s]);
+        }
+        exact[k] = own;
+        rtq::requantise(W, box, inflate);
     }
     return RT_OK;
 }

@@ -135,6 +135,16 @@ class ShadeInfo(ctypes.Structure):  # rt_shade_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+class VertexUpdate(ctypes.Structure):  # rt_vertex_update
+    _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
+
+
+class UpdateInfo(ctypes.Structure):  # rt_update_info
+    _fields_ = [("views_refit", ctypes.c_int), ("views_rebuilt", ctypes.c_int), ("joined_unit", ctypes.c_int),
+                ("joined_primary", ctypes.c_int), ("scene_magnitude", ctypes.c_float), ("area_ratio", ctypes.c_float),
+                ("update_ms", ctypes.c_float)]
+
+
 _host = None
 _hip = None
 
@@ -167,6 +177,10 @@ def host():
                                     P(ctypes.c_int), P(P(ctypes.c_int)), P(BvhStats)]
         L.rth_wbvh_build.argtypes = [P(BvhNode), ctypes.c_int, P(ctypes.c_int), P(Triangle), ctypes.c_int,
                                      ctypes.c_float, P(P(ctypes.c_uint32)), P(P(ctypes.c_int)), P(WbvhInfo)]
+        L.rth_wbvh_refit.argtypes = [P(ctypes.c_uint32), ctypes.c_int, P(ctypes.c_int), P(Triangle), ctypes.c_int,
+                                     ctypes.c_float]
+        L.rth_triangle_init.argtypes = [P(Triangle), P(Vec3), P(Vec3), P(Vec3), P(Vec3), P(Vec3), P(Vec3)]
+        L.rth_triangle_init.restype = None
         L.rth_triangles_load_cached.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                                 P(P(Triangle)), P(ctypes.c_size_t), P(ctypes.c_int)]
         L.rth_bvh_build_cached.argtypes = [P(Triangle), ctypes.c_size_t, ctypes.c_int, P(Rng), ctypes.c_char_p,
@@ -221,6 +235,11 @@ def hip():
         L.rt_get_query_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
         L.rt_shade_rays.argtypes = [ctypes.c_void_p, P(Shade), P(ShadeResults)]
         L.rt_get_shade_info.argtypes = [ctypes.c_void_p, P(ShadeInfo)]
+        L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
+        L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
+        L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]
+        L.rt_debug_read_wide.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_int]
         L.rt_device_count.argtypes = []
         L.rt_version.restype = ctypes.c_char_p
         _hip = L

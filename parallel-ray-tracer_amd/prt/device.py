@@ -439,6 +439,54 @@ class Renderer:
         self._chk(_L.rt_get_shade_info(self._ctx, ctypes.byref(i)), "rt_get_shade_info")
         return {f: getattr(i, f) for f, _ in _lib.ShadeInfo._fields_}
 
+    def update_vertices(self, coords):
+        """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
+        coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original
+        order), e.g. a physics step's output. Afterwards every render and query gives the bits a fresh upload of the
+        moved scene (same materials, same reference tree with regrown boxes) gives. Read in stream order on the
+        renderer's stream; a non-finite coordinate or another triangle count is refused and changes nothing."""
+        import torch
+        if not isinstance(coords, torch.Tensor):
+            raise RtError(f"coords: expected a torch tensor, got {type(coords).__name__}")
+        if coords.dim() != 3 or tuple(coords.shape[1:]) != (3, 3):
+            raise RtError(f"coords: shape {tuple(coords.shape)}, expected [n, 3, 3]")
+        n = coords.shape[0]
+        u = _lib.VertexUpdate(_ptr(coords, "coords", 9 * n, (torch.float32,), self.device), n)
+        self._chk(_L.rt_update_vertices(self._ctx, ctypes.byref(u)), "rt_update_vertices")
+
+    def update_info(self):
+        """rt_get_update_info: what the last update_vertices did (views refitted / rebuilt, the triangles that joined
+        the unit and the primary view, the new scene magnitude, the full view's area_ratio against its build) and
+        update_ms; synchronises"""
+        i = _lib.UpdateInfo()
+        self._chk(_L.rt_get_update_info(self._ctx, ctypes.byref(i)), "rt_get_update_info")
+        return {f: getattr(i, f) for f, _ in _lib.UpdateInfo._fields_}
+
+    def update_lights(self, lights):
+        """rt_update_lights: new positions / colours for the uploaded lights (a LIGHT_DTYPE array of the same length)"""
+        from .host import LIGHT_DTYPE
+        lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        self._chk(_L.rt_update_lights(self._ctx, lights.ctypes.data_as(P(Light)) if len(lights) else None, len(lights)),
+                  "rt_update_lights")
+
+    def _debug_wide(self, view="full"):
+        """test-only (rt_debug_read_wide): a wide view's node words [n, 20] uint32 and its position -> original
+        triangle map as they stand on the device, or (None, None) without that view; synchronises"""
+        v = {"full": 0, "unit": 1, "primary": 2}[view]
+        n = _L.rt_debug_read_wide(self._ctx, v, None, 0, None, 0)
+        if n < 0:
+            self._chk(n, "rt_debug_read_wide")
+        if n == 0:
+            return None, None
+        info = self.scene_info()
+        nt = {0: info["n_triangles"], 1: info["unit_triangles"], 2: info["primary_triangles"]}[v]
+        words = np.zeros((n, 20), np.uint32)
+        orig = np.zeros(nt, np.int32)
+        got = _L.rt_debug_read_wide(self._ctx, v, words.ctypes.data, n, orig.ctypes.data, nt)
+        if got < 0:
+            self._chk(got, "rt_debug_read_wide")
+        return words, orig
+
     def stats(self):
         s = Stats()
         self._chk(_L.rt_get_stats(self._ctx, ctypes.byref(s)), "rt_get_stats")

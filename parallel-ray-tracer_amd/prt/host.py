@@ -138,6 +138,36 @@ def wbvh_build(nodes, tri_idx, tris, inflate=0.0):
     return w, o, {"n_nodes": info.n_nodes, "depth": info.depth, "max_children": info.max_children}
 
 
+def wbvh_refit(words, tri_order, tris, inflate=0.0):
+    """rth_wbvh_refit: a built wide tree's boxes for the same triangles at new coordinates (topology words kept)
+    -> a new words array [n_nodes, 20]; the CPU reference of the device refit (Renderer.update_vertices)"""
+    w = np.array(words, dtype=np.uint32, order="C", copy=True)
+    tri_order = np.ascontiguousarray(tri_order, dtype=np.int32)
+    tris = np.ascontiguousarray(tris, dtype=TRI_DTYPE)
+    _check(_lib.host().rth_wbvh_refit(w.ctypes.data_as(P(ctypes.c_uint32)), len(w),
+                                      tri_order.ctypes.data_as(P(ctypes.c_int)), tris.ctypes.data_as(P(Triangle)),
+                                      len(tris), float(inflate)), "wbvh_refit")
+    return w
+
+
+def triangle_init(coords, ks, kd, kr):
+    """triangle_init(t, a, b, c, ks, kd, kr), cpu/src/triangle.c:6-24, for arrays: coords [n, 3, 3], ks / kd / kr
+    [n, 3] -> n triangles (centroid and both normals computed by the library, rth_triangle_init)"""
+    L = _lib.host()
+    coords = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3, 3)
+    n = len(coords)
+    mats = [np.ascontiguousarray(np.broadcast_to(np.asarray(m, np.float32), (n, 3))) for m in (ks, kd, kr)]
+    out = np.zeros(n, TRI_DTYPE)
+    V = ctypes.sizeof(_lib.Vec3)
+    T = ctypes.sizeof(Triangle)
+    at = lambda arr, off: ctypes.cast(arr.ctypes.data + off, P(_lib.Vec3))  # noqa: E731
+    for i in range(n):
+        L.rth_triangle_init(ctypes.cast(out.ctypes.data + i * T, P(Triangle)), at(coords, (3 * i) * V),
+                            at(coords, (3 * i + 1) * V), at(coords, (3 * i + 2) * V), at(mats[0], i * V),
+                            at(mats[1], i * V), at(mats[2], i * V))
+    return out
+
+
 def wbvh_decode(words):
     """decoded view of wide nodes: p [N,3] f32, scale [N,3] f32, imask [N], child_base [N], tri_base [N],
     meta [N,8] u8, qlo/qhi [N,3,8] u8 and the decoded child boxes lo/hi [N,8,3] (fmaf(scale, 1024 + q, p): the planes'
