@@ -28,7 +28,7 @@ cli: $(BIN)/raytracer
 
 HOST_SRCS := $(CSRC)/host/rt_host.cpp $(CSRC)/host/rt_wide.cpp $(CSRC)/host/rt_cache.cpp
 
-HOST_HDRS := include/rt_host.h include/rt_types.h $(CSRC)/hip/rt_quant.hpp
+HOST_HDRS := include/rt_host.h include/rt_types.h $(CSRC)/hip/rt_quant.hpp $(CSRC)/hip/rt_collapse.hpp
 
 $(LIB)/librt_host.so: $(HOST_SRCS) $(HOST_HDRS)
 	@mkdir -p $(LIB)

@@ -414,6 +414,64 @@ int rt_update_lights(rt_ctx* ctx, const rt_light* lights, int n_lights);
  * tests/test_gpu_refit.py compares the words with rth_wbvh_refit's. Not part of the supported interface. */
 int rt_debug_read_wide(rt_ctx* ctx, int view, unsigned int* nodes, int cap_nodes, int* tri_orig, int cap_tris);
 
+/* ---- view rebuilds: new topologies for the fast walk's wide views after large motion.
+ * rt_update_vertices keeps every tree's topology; after large motion the wide views' boxes overlap and frames slow down
+ * (rt_update_info.area_ratio). rt_rebuild_views does everything rt_update_vertices does for the same coords -- the plan
+ * pass with its refusals, records, normals, reference tree, binary acceleration view, faces, a refit of the wide views
+ * -- and then gives the wide views (full, unit, primary) a new topology built from those device-resident coordinates.
+ * The reference tree is kept, so every render, ray query and radiance query, strict kernel and every fast variant,
+ * returns exactly the bits it returns after rt_update_vertices of the same coords: the fast walk gives the reference's
+ * bits on any conservative BVH, the views only change speed.
+ * The subset views follow the upload's rule over the new coordinates (hittable triangles, and only when there are some
+ * and fewer than the upload's limits): a view may appear, disappear or change size exactly as in a fresh upload.
+ * The new views are built into fresh buffers and swapped in in stream order; the old ones and their refit data are
+ * freed; rt_update_info.area_ratio is measured against the rebuilt view from then on; rt_scene_info's view fields follow.
+ * The default rule's per-shape launch decisions survive, query / shade / update-info state is untouched.
+ * Modes:
+ *   RT_REBUILD_HOST    the upload's own path over downloaded coordinates (PLOC or binned SAH as the scene was built,
+ *                      the host treelet pass, the cost-optimal collapse): the quality of a fresh upload.
+ *   RT_REBUILD_DEVICE  no tree leaves the device: subset compaction, PLOC from the device vertices, the greedy collapse
+ *                      (rt_collapse.hpp; no treelet pass, no cost model), then the refit's own fill of boxes and records.
+ *                      The host reads back a few counts per PLOC round and per wide level. Only for a scene whose
+ *                      accel_built is RT_ACCEL_GPU (RT_E_ARG otherwise); RT_E_STATE, with the refitted scene left in
+ *                      place, when a device tree is deeper than the wide walk's stack.
+ *   RT_REBUILD_AUTO    DEVICE where it is allowed, falling back to HOST when a device tree is too deep or larger than
+ *                      the packed layouts' node bound; HOST for a host-built scene.
+ * Errors: RT_E_STATE before an upload and for a scene without a wide view (RT_ACCEL_REFERENCE); the update's own errors
+ * and refusals unchanged (a non-finite coordinate changes nothing). A failure after the update step returns its error
+ * and leaves the refitted scene, which is valid. The call waits on the host (counts, and in HOST mode the whole build). */
+enum { RT_REBUILD_AUTO = 0, RT_REBUILD_DEVICE = 1, RT_REBUILD_HOST = 2 };
+typedef struct rt_view_rebuild {
+    const float* coords;  /* device, [n_triangles][3][3] f32, as rt_vertex_update.coords */
+    int n_triangles;      /* must equal the uploaded scene's */
+    int mode;             /* RT_REBUILD_* */
+} rt_view_rebuild;
+int rt_rebuild_views(rt_ctx* ctx, const rt_view_rebuild* r);
+
+typedef struct rt_rebuild_info {
+    int mode_used;            /* RT_REBUILD_DEVICE or RT_REBUILD_HOST */
+    int fell_back;            /* RT_REBUILD_AUTO on a GPU-built scene used HOST: 1 too deep, 2 too many nodes; else 0 */
+    int views_built;          /* wide views built (1..3) */
+    int nodes[3], depth[3];   /* per view (full, unit, primary): wide nodes and levels; 0: no such view now */
+    int launches;             /* DEVICE: kernel launches and copies issued by the build (PLOC, collapse, fill) */
+    double area_before;       /* full view: summed decoded child-box area just after the refit ... */
+    double area_after;        /* ... and just after the rebuild (rt_refit.hpp k_wide_area) */
+    float rebuild_ms;         /* HIP events on the context stream around the whole call's device work */
+    float host_ms;            /* the call's wall time */
+    float ploc_ms, collapse_ms, fill_ms; /* wall time of the stages, summed over the views (HOST: ploc includes the
+                                            treelet pass, fill the upload of the views) */
+} rt_rebuild_info;
+/* of the last rebuild (synchronises); RT_E_STATE before the first rebuild */
+int rt_get_rebuild_info(rt_ctx* ctx, rt_rebuild_info* info);
+
+/* Test-only read-back of the binary tree the last RT_REBUILD_DEVICE rebuild collapsed for a view (0 = full, 1 = unit,
+ * 2 = primary), so that the CPU mirror (rth_wbvh_build_greedy) can be given the same input. Layout: a view of n
+ * triangles has nodes 0 .. n - 1 = leaves, leaf k holding scene triangle leaf_tri[k], and nodes n .. 2 n - 2 = merges
+ * whose children are left[id - n] and right[id - n]; *root is the root's id. Returns n (0: no such view or no device
+ * rebuild) or < 0; copies min(n, cap) leaf_tri entries and min(n - 1, cap) left / right entries (all nullable).
+ * Not part of the supported interface. */
+int rt_debug_read_build_tree(rt_ctx* ctx, int view, int* left, int* right, int* leaf_tri, int cap, int* root);
+
 /* load_from_gpu(): copies the last frame's compact rows to host (synchronous); nullable args. RT_E_KERNEL when the
  * render reported a traversal-stack overflow (its frame is not valid). */
 int rt_download(rt_ctx* ctx, float* h_rgb, int* h_hit);

@@ -90,6 +90,30 @@ int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const int* tri_idx,
 int rth_wbvh_refit(uint32_t* nodes, int n_nodes, const int* tri_order, const rt_triangle* tris, int n_tris,
                    float inflate);
 
+/* The greedy collapse (rt_collapse.hpp), the CPU mirror of the device's view rebuild (rt_rebuild_views, RT_REBUILD_DEVICE):
+ * the same inputs and outputs as rth_wbvh_build. A wide node starts from a binary node's two children and repeatedly
+ * opens the open child of largest box area that is interior and holds more than 4 triangles (ties: the leftmost; the
+ * opened child's two children take its place), until it has 8 children or none can be opened; a child of at most 4
+ * triangles becomes a leaf slot. No cost model, no treelet pass. Nodes are laid out breadth first, a level's child and
+ * triangle bases being running sums in node order; the boxes are rth_wbvh_refit's over that topology. The device runs
+ * the same header per node and is held to these words bit for bit (tests/test_gpu_rebuild.py). */
+int rth_wbvh_build_greedy(const rt_bvh_node* bvh, int n_nodes, const int* tri_idx, const rt_triangle* tris, int n_tris,
+                          float inflate, uint32_t** nodes, int** tri_order, rth_wbvh_info* info);
+
+/* Structural validator of a wide tree's words (any builder's). Returns 0 and fills info (nullable), or the code of the
+ * first violated property, checked in this order over the whole tree: */
+enum {
+    RTH_WCHK_LEAF = -101,   /* a leaf slot holds 0 or more than 4 triangles (or an interior slot has a meta byte) */
+    RTH_WCHK_RANGE = -102,  /* a child index or a triangle range is out of bounds */
+    RTH_WCHK_PARENT = -103, /* a node other than the root has no parent or several, or the root has one */
+    RTH_WCHK_LEVELS = -104, /* the levels are not contiguous breadth-first ranges */
+    RTH_WCHK_COVER = -105,  /* a wide-leaf position 0 .. n_tris - 1 is covered twice or never */
+    RTH_WCHK_ORDER = -106,  /* tri_order is not injective into 0 .. n_tris - 1 */
+    RTH_WCHK_DEPTH = -107   /* deeper than max_depth (max_depth <= 0: not checked) */
+};
+int rth_wbvh_check(const uint32_t* nodes, int n_nodes, const int* tri_order, int n_tris, int max_depth,
+                   rth_wbvh_info* info);
+
 /* ---- camera: cam_init + cam.rot.x + cam_calculate_screen_coords + inc_x/inc_y
  * (cpu/src/cam.c:5-48, main.c:105-106, main.c:243-250) for a width x height frame:
  * pos (0,-9,3), fov pi/3.2, rot.x = -pi/12. */

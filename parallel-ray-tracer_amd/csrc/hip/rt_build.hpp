@@ -9,11 +9,13 @@
 //                     positions of the sorted cluster array; mutually nearest pairs merge into a new node
 //                     (k_flags, scans, k_merge: node ids by prefix sum, so the tree is deterministic), the
 //                     survivors are compacted (k_compact) — until one cluster is left
-// The binary tree (children, boxes) goes back to the host, where rt_hip.hip lays it out as a reference-layout
+// At an upload the binary tree (children, boxes) goes back to the host, where rt_hip.hip lays it out as a reference-layout
 // BVH (children consecutive, leaf triangles in depth-first order so that every subtree's triangles are one
 // range) and the 8-wide collapse + outward quantisation (rt_wide.cpp) runs as for the host-built tree. Any
 // conservative BVH renders the same bits (the fast walk returns the minimum t over all triangles, ties
-// re-walked strictly), so the tree only changes speed.
+// re-walked strictly), so the tree only changes speed. A view rebuild (rt_rebuild_views) keeps the tree on the device and
+// collapses it there (rt_collapse.hpp): the build proper (rt_hip.hip ploc_build) reads a device vertex array and is
+// shared by both.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,13 +88,14 @@ __global__ __launch_bounds__(256) void k_morton(const float4* __restrict__ lo, c
 // leaves: node k = sorted triangle sorted[k]; the clusters start as the leaves in Morton order
 __global__ __launch_bounds__(256) void k_leaves(const int* __restrict__ sorted, const float4* __restrict__ plo,
                                                 const float4* __restrict__ phi, int n, float4* __restrict__ nlo,
-                                                float4* __restrict__ nhi, int* __restrict__ C) {
+                                                float4* __restrict__ nhi, int* __restrict__ C, int* __restrict__ cnt) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const int t = sorted[k];
     nlo[k] = plo[t];
     nhi[k] = phi[t];
     C[k] = k;
+    cnt[k] = 1;
 }
 
 __device__ __forceinline__ float merged_area(float4 alo, float4 ahi, float4 blo, float4 bhi) {
@@ -146,11 +149,12 @@ __global__ __launch_bounds__(256) void k_flags(const int* __restrict__ nn, int m
     keep[i] = !(mutual && i > j);
 }
 
-// node id base + moff[i] = union of C[i] and C[nn[i]]; children of internal node id at left / right[id - n]
+// node id base + moff[i] = union of C[i] and C[nn[i]]; children of internal node id at left / right[id - n]; cnt: every
+// node's triangle count (the device collapse's leaf rule, rt_collapse.hpp)
 __global__ __launch_bounds__(256) void k_merge(int* __restrict__ C, const int* __restrict__ nn,
                                                const int* __restrict__ mflag, const int* __restrict__ moff, int m,
                                                int n, int base, float4* __restrict__ nlo, float4* __restrict__ nhi,
-                                               int* __restrict__ left, int* __restrict__ right) {
+                                               int* __restrict__ left, int* __restrict__ right, int* __restrict__ cnt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m || !mflag[i]) return;
     const int a = C[i], b = C[nn[i]], id = base + moff[i];
@@ -159,6 +163,7 @@ __global__ __launch_bounds__(256) void k_merge(int* __restrict__ C, const int* _
     nhi[id] = make_float4(fmaxf(ahi.x, bhi.x), fmaxf(ahi.y, bhi.y), fmaxf(ahi.z, bhi.z), 0.0f);
     left[id - n] = a;
     right[id - n] = b;
+    cnt[id] = cnt[a] + cnt[b];
     C[i] = id;
 }
 

@@ -34,6 +34,7 @@
 #include "rt_query.hpp"
 #include "rt_shade.hpp"
 #include "rt_refit.hpp"
+#include "rt_collapse.hpp"
 #ifndef PRT_TREELET
 #define PRT_TREELET 2  // treelet-restructuring passes over the GPU-built binary tree (0: none)
 #endif
@@ -191,7 +192,7 @@ struct rt_ctx {
     RefitTopo tp_ref, tp_acc, tp_wide, tp_unit, tp_prim;
     unsigned* d_plan = nullptr;  // [rtr::P_WORDS]
     unsigned* h_plan = nullptr;  // pinned
-    double* d_area = nullptr;    // [2]: the full view's decoded child-box area when it was built, and now
+    double* d_area = nullptr;    // [5]: the full view's decoded child-box area when it was built, and now (then the rebuilds')
     bool area_base = false;      // d_area[0] holds the current build's
     float* d_face_tmp = nullptr; // unsorted faces [3][4 records]
     void* d_sort_tmp = nullptr;
@@ -201,6 +202,17 @@ struct rt_ctx {
     hipEvent_t u_evs = nullptr;                   // the start of the update under way (u_ev0 once it is made)
     bool updated = false;
     rt_update_info uinfo{};
+    // view rebuilds (rt_rebuild_views, rt_collapse.hpp): the binary tree the last device rebuild collapsed per view (test
+    // read-back, rt_debug_read_build_tree), the events around the last rebuild and its report. d_area[2], [3]: the full
+    // view's area just after the last rebuild and just before it; [4]: the accumulator of the rebuild under way
+    struct BuildTree {
+        int *left = nullptr, *right = nullptr, *leaf = nullptr;
+        int n = 0, root = 0;
+    } bt[3];
+    hipEvent_t r_ev0 = nullptr, r_ev1 = nullptr;  // around the last rebuild made
+    hipEvent_t r_evs = nullptr;                   // the start of the rebuild under way (r_ev0 once it is made)
+    bool rebuilt = false;
+    rt_rebuild_info rinfo{};
     float4* h_lights = nullptr;  // pinned staging of rt_update_lights, 2 x n_lights (freed with the scene)
     hipEvent_t lights_ev = nullptr;
     float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
@@ -319,7 +331,15 @@ void free_topo(RefitTopo& t) {
     t = RefitTopo();
 }
 
+void free_build_tree(rt_ctx::BuildTree& b) {
+    for (void* p : {(void*)b.left, (void*)b.right, (void*)b.leaf})
+        if (p) (void)hipFree(p);
+    b = rt_ctx::BuildTree();
+}
+
 void free_scene(rt_ctx* ctx) {
+    for (rt_ctx::BuildTree& b : ctx->bt) free_build_tree(b);
+    ctx->rebuilt = false;
     for (RefitTopo* t : {&ctx->tp_ref, &ctx->tp_acc, &ctx->tp_wide, &ctx->tp_unit, &ctx->tp_prim}) free_topo(*t);
     for (void* p : {(void*)ctx->d_face_tmp, ctx->d_sort_tmp})
         if (p) (void)hipFree(p);
@@ -531,6 +551,95 @@ int build_threads() {
     const unsigned hc = std::thread::hardware_concurrency();
     return (int)std::max(1u, std::min(16u, hc));
 }
+// PLOC's device arrays (rt_build.hpp) for n triangles: what the build proper (ploc_build) works in and leaves -- the
+// binary tree in left / right (children of node n + j), every node's box (nlo / nhi) and triangle count (cnt), the
+// leaves' triangles (sorted) and the root's id in C[0].
+struct PlocDev {
+    int n = 0;
+    float4 *plo = nullptr, *phi = nullptr, *nlo = nullptr, *nhi = nullptr;
+    unsigned *keys = nullptr, *keys2 = nullptr;
+    int *vals = nullptr, *sorted = nullptr, *cb = nullptr, *C = nullptr, *C2 = nullptr, *nnb = nullptr, *mflag = nullptr,
+        *keep = nullptr, *moff = nullptr, *koff = nullptr, *left = nullptr, *right = nullptr, *cnt = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    int* tot = nullptr;  // pinned: a merge round's merge and survivor totals
+    int rounds = 0;
+    void release() {
+        if (tot) (void)hipHostFree(tot);
+        for (void* p : {(void*)plo, (void*)phi, (void*)nlo, (void*)nhi, (void*)keys, (void*)keys2, (void*)vals,
+                        (void*)sorted, (void*)cb, (void*)C, (void*)C2, (void*)nnb, (void*)mflag, (void*)keep, (void*)moff,
+                        (void*)koff, (void*)left, (void*)right, (void*)cnt, tmp})
+            if (p) (void)hipFree(p);
+        *this = PlocDev();
+    }
+};
+
+int ploc_alloc(rt_ctx* ctx, PlocDev& P, int n) {
+    P.n = n;
+    const size_t nn2 = 2 * (size_t)n;
+    HIPC(hipMalloc((void**)&P.plo, sizeof(float4) * n));
+    HIPC(hipMalloc((void**)&P.phi, sizeof(float4) * n));
+    HIPC(hipMalloc((void**)&P.nlo, sizeof(float4) * nn2));
+    HIPC(hipMalloc((void**)&P.nhi, sizeof(float4) * nn2));
+    HIPC(hipMalloc((void**)&P.keys, sizeof(unsigned) * n));
+    HIPC(hipMalloc((void**)&P.keys2, sizeof(unsigned) * n));
+    for (int** p : {&P.vals, &P.sorted, &P.C, &P.C2, &P.nnb, &P.mflag, &P.keep, &P.moff, &P.koff})
+        HIPC(hipMalloc((void**)p, sizeof(int) * n));
+    HIPC(hipMalloc((void**)&P.left, sizeof(int) * std::max(1, n - 1)));
+    HIPC(hipMalloc((void**)&P.right, sizeof(int) * std::max(1, n - 1)));
+    HIPC(hipMalloc((void**)&P.cnt, sizeof(int) * nn2));
+    HIPC(hipMalloc((void**)&P.cb, sizeof(int) * 8));
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, P.keys, P.keys2, P.vals, P.sorted, n, 0, 30, ctx->stream));
+    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, P.mflag, P.moff, n, ctx->stream));
+    P.tmp_bytes = std::max(sort_bytes, scan_bytes);
+    HIPC(hipMalloc(&P.tmp, P.tmp_bytes));
+    HIPC(hipHostMalloc((void**)&P.tot, sizeof(int) * 4, hipHostMallocDefault));
+    return RT_OK;
+}
+
+// The device build proper over the device vertex array dv (9 floats per triangle), in stream order; waits for the
+// stream once per merge round (the round's totals). RT_E_STATE: no progress (never expected).
+int ploc_build(rt_ctx* ctx, PlocDev& P, const float* dv, int R) {
+    hipStream_t st = ctx->stream;
+    const int n = P.n;
+    const int cb_init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
+    HIPC(hipMemcpyAsync(P.cb, cb_init, sizeof cb_init, hipMemcpyHostToDevice, st));
+    const int g = (n + 255) / 256;
+    rtb::k_prim_boxes<<<g, 256, 0, st>>>(dv, n, P.plo, P.phi, P.cb);
+    rtb::k_morton<<<g, 256, 0, st>>>(P.plo, P.phi, n, P.cb, P.keys, P.vals);
+    HIPC(hipGetLastError());
+    size_t sort_bytes = P.tmp_bytes;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(P.tmp, sort_bytes, P.keys, P.keys2, P.vals, P.sorted, n, 0, 30, st));
+    rtb::k_leaves<<<g, 256, 0, st>>>(P.sorted, P.plo, P.phi, n, P.nlo, P.nhi, P.C, P.cnt);
+    HIPC(hipGetLastError());
+    int m = n, next = n;
+    P.rounds = 0;
+    while (m > 1) {
+        const int gm = (m + 255) / 256;
+        rtb::k_nn<<<gm, 256, 0, st>>>(P.C, m, P.nlo, P.nhi, P.nnb, R);
+        rtb::k_flags<<<gm, 256, 0, st>>>(P.nnb, m, P.mflag, P.keep);
+        size_t b1 = P.tmp_bytes, b2 = P.tmp_bytes;
+        HIPC(hipcub::DeviceScan::ExclusiveSum(P.tmp, b1, P.mflag, P.moff, m, st));
+        HIPC(hipcub::DeviceScan::ExclusiveSum(P.tmp, b2, P.keep, P.koff, m, st));
+        HIPC(hipMemcpyAsync(P.tot, P.moff + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(P.tot + 1, P.mflag + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(P.tot + 2, P.koff + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(P.tot + 3, P.keep + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        rtb::k_merge<<<gm, 256, 0, st>>>(P.C, P.nnb, P.mflag, P.moff, m, n, next, P.nlo, P.nhi, P.left, P.right, P.cnt);
+        rtb::k_compact<<<gm, 256, 0, st>>>(P.C, P.keep, P.koff, m, P.C2);
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(st));
+        const int merges = P.tot[0] + P.tot[1], survivors = P.tot[2] + P.tot[3];
+        if (merges <= 0 || survivors != m - merges) return RT_E_STATE;  // no progress: a mutual pair always exists
+        next += merges;
+        m = survivors;
+        std::swap(P.C, P.C2);
+        P.rounds++;
+    }
+    return RT_OK;
+}
+
 // GPU-built acceleration BVH (rt_build.hpp, PLOC) in the reference layout: children of a node at child and
 // child + 1, single-triangle leaves numbered depth-first (every subtree's triangles are one range of idx).
 // Returns RT_OK, or RT_E_STATE when the tree is unusable (the caller falls back to the host build).
@@ -547,21 +656,11 @@ int gpu_ploc(rt_ctx* ctx, const rt_triangle* T, int n, int R, std::vector<rt_bvh
         }
     const size_t nn2 = 2 * (size_t)n;
     float* dv = nullptr;
-    float4 *plo = nullptr, *phi = nullptr, *nlo = nullptr, *nhi = nullptr;
-    unsigned *keys = nullptr, *keys2 = nullptr;
-    int *vals = nullptr, *sorted = nullptr, *cb = nullptr, *C = nullptr, *C2 = nullptr, *nnb = nullptr, *mflag = nullptr,
-        *keep = nullptr, *moff = nullptr, *koff = nullptr, *left = nullptr, *right = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    int* tot = nullptr;  // pinned: a merge round's merge and survivor totals
+    PlocDev P;
     int rc = RT_OK;
     auto done = [&]() {
-        if (tot) (void)hipHostFree(tot);
-        tot = nullptr;
-        for (void* p : {(void*)dv, (void*)plo, (void*)phi, (void*)nlo, (void*)nhi, (void*)keys, (void*)keys2, (void*)vals,
-                        (void*)sorted, (void*)cb, (void*)C, (void*)C2, (void*)nnb, (void*)mflag, (void*)keep, (void*)moff,
-                        (void*)koff, (void*)left, (void*)right, tmp})
-            if (p) (void)hipFree(p);
+        if (dv) (void)hipFree(dv);
+        P.release();
         return rc;
     };
 #define PLOC(call)                                   \
@@ -573,57 +672,11 @@ int gpu_ploc(rt_ctx* ctx, const rt_triangle* T, int n, int R, std::vector<rt_bvh
         }                                            \
     } while (0)
     PLOC(hipMalloc((void**)&dv, sizeof(float) * hv.size()));
-    PLOC(hipMalloc((void**)&plo, sizeof(float4) * n));
-    PLOC(hipMalloc((void**)&phi, sizeof(float4) * n));
-    PLOC(hipMalloc((void**)&nlo, sizeof(float4) * nn2));
-    PLOC(hipMalloc((void**)&nhi, sizeof(float4) * nn2));
-    PLOC(hipMalloc((void**)&keys, sizeof(unsigned) * n));
-    PLOC(hipMalloc((void**)&keys2, sizeof(unsigned) * n));
-    for (int** p : {&vals, &sorted, &C, &C2, &nnb, &mflag, &keep, &moff, &koff}) PLOC(hipMalloc((void**)p, sizeof(int) * n));
-    PLOC(hipMalloc((void**)&left, sizeof(int) * std::max(1, n - 1)));
-    PLOC(hipMalloc((void**)&right, sizeof(int) * std::max(1, n - 1)));
-    PLOC(hipMalloc((void**)&cb, sizeof(int) * 8));
+    if ((rc = ploc_alloc(ctx, P, n))) return done();
     PLOC(hipMemcpyAsync(dv, hv.data(), sizeof(float) * hv.size(), hipMemcpyHostToDevice, st));
-    const int cb_init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-    PLOC(hipMemcpyAsync(cb, cb_init, sizeof cb_init, hipMemcpyHostToDevice, st));
-    const int g = (n + 255) / 256;
-    rtb::k_prim_boxes<<<g, 256, 0, st>>>(dv, n, plo, phi, cb);
-    rtb::k_morton<<<g, 256, 0, st>>>(plo, phi, n, cb, keys, vals);
-    PLOC(hipGetLastError());
-    size_t sort_bytes = 0, scan_bytes = 0;
-    PLOC(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys2, vals, sorted, n, 0, 30, st));
-    PLOC(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, mflag, moff, n, st));
-    tmp_bytes = std::max(sort_bytes, scan_bytes);
-    PLOC(hipMalloc(&tmp, tmp_bytes));
-    PLOC(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, keys, keys2, vals, sorted, n, 0, 30, st));
-    rtb::k_leaves<<<g, 256, 0, st>>>(sorted, plo, phi, n, nlo, nhi, C);
-    PLOC(hipGetLastError());
-    int m = n, next = n;
-    PLOC(hipHostMalloc((void**)&tot, sizeof(int) * 4, hipHostMallocDefault));
-    while (m > 1) {
-        const int gm = (m + 255) / 256;
-        rtb::k_nn<<<gm, 256, 0, st>>>(C, m, nlo, nhi, nnb, R);
-        rtb::k_flags<<<gm, 256, 0, st>>>(nnb, m, mflag, keep);
-        size_t b1 = tmp_bytes, b2 = tmp_bytes;
-        PLOC(hipcub::DeviceScan::ExclusiveSum(tmp, b1, mflag, moff, m, st));
-        PLOC(hipcub::DeviceScan::ExclusiveSum(tmp, b2, keep, koff, m, st));
-        PLOC(hipMemcpyAsync(tot, moff + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-        PLOC(hipMemcpyAsync(tot + 1, mflag + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-        PLOC(hipMemcpyAsync(tot + 2, koff + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-        PLOC(hipMemcpyAsync(tot + 3, keep + m - 1, sizeof(int), hipMemcpyDeviceToHost, st));
-        rtb::k_merge<<<gm, 256, 0, st>>>(C, nnb, mflag, moff, m, n, next, nlo, nhi, left, right);
-        rtb::k_compact<<<gm, 256, 0, st>>>(C, keep, koff, m, C2);
-        PLOC(hipGetLastError());
-        PLOC(hipStreamSynchronize(st));
-        const int merges = tot[0] + tot[1], survivors = tot[2] + tot[3];
-        if (merges <= 0 || survivors != m - merges) {  // no progress: never expected (a mutual pair always exists)
-            rc = RT_E_STATE;
-            return done();
-        }
-        next += merges;
-        m = survivors;
-        std::swap(C, C2);
-    }
+    if ((rc = ploc_build(ctx, P, dv, R))) return done();
+    const int *C = P.C, *left = P.left, *right = P.right, *sorted = P.sorted;
+    const float4 *nlo = P.nlo, *nhi = P.nhi;
     // the tree back to the host
     const int ni = n - 1;
     std::vector<int> hl(std::max(ni, 1)), hr(std::max(ni, 1)), hs(n);
@@ -2324,7 +2377,10 @@ int rebuild_subset(rt_ctx* ctx, const rt_scene* s2, double dmax, size_t fewer_th
 
 }  // namespace
 
-extern "C" int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u) {
+namespace {
+// rt_update_vertices; report: the update becomes the one rt_get_update_info answers for (a view rebuild runs the same
+// update without touching that state); inflate_out (nullable): the new inflation
+int update_vertices(rt_ctx* ctx, const rt_vertex_update* u, bool report, float* inflate_out) {
     if (!ctx) return RT_E_ARG;
     if (!ctx->has_scene) {
         ctx->err = "rt_update_vertices: no scene uploaded";
@@ -2337,7 +2393,7 @@ extern "C" int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u) {
     const int n = ctx->n_tris;
     const float* coords = u->coords;
     if (!ctx->d_plan) HIPC(hipMalloc((void**)&ctx->d_plan, sizeof(unsigned) * rtr::P_WORDS));
-    if (!ctx->d_area) HIPC(hipMalloc((void**)&ctx->d_area, sizeof(double) * 2));
+    if (!ctx->d_area) HIPC(hipMalloc((void**)&ctx->d_area, sizeof(double) * 5));
     if (!ctx->h_plan) HIPC(hipHostMalloc((void**)&ctx->h_plan, sizeof(unsigned) * rtr::P_WORDS, hipHostMallocDefault));
     if (!ctx->u_ev0) HIPC(hipEventCreate(&ctx->u_ev0));
     if (!ctx->u_ev1) HIPC(hipEventCreate(&ctx->u_ev1));
@@ -2430,13 +2486,18 @@ extern "C" int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u) {
         if ((rc = refit_wide(ctx, ctx->prim, ctx->tp_prim, coords, inflate, nullptr))) return rc;
         ui.views_refit++;
     }
+    ctx->scene_mx = scene_mx;
+    if (inflate_out) *inflate_out = inflate;
+    if (!report) return RT_OK;
     std::swap(ctx->u_ev0, ctx->u_evs);
     HIPC(hipEventRecord(ctx->u_ev1, st));
-    ctx->scene_mx = scene_mx;
     ctx->uinfo = ui;
     ctx->updated = true;
     return RT_OK;
 }
+}  // namespace
+
+extern "C" int rt_update_vertices(rt_ctx* ctx, const rt_vertex_update* u) { return update_vertices(ctx, u, true, nullptr); }
 
 extern "C" int rt_get_update_info(rt_ctx* ctx, rt_update_info* info) {
     if (!ctx || !info) return RT_E_ARG;
@@ -2493,6 +2554,390 @@ extern "C" int rt_debug_read_wide(rt_ctx* ctx, int view, unsigned int* nodes, in
     if (nodes && nn > 0) HIPC(hipMemcpy(nodes, w.nodes, sizeof(unsigned) * 20 * (size_t)nn, hipMemcpyDeviceToHost));
     if (tri_orig && nt > 0) HIPC(hipMemcpy(tri_orig, w.orig, sizeof(int) * (size_t)nt, hipMemcpyDeviceToHost));
     return w.n;
+}
+
+// ---------------------------------------------------------------- view rebuilds (rt_collapse.hpp)
+namespace {
+
+using clk = std::chrono::steady_clock;
+float ms_since(clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); }
+
+// A wide view built for a rebuild, not yet part of the context: the view, its refit data (made with it: the levels are
+// known here) and, from the device path, the binary tree it was collapsed from.
+struct NewView {
+    DevWide w;
+    RefitTopo t;
+    rt_ctx::BuildTree bt;
+    void release() {
+        free_wide(w);
+        free_topo(t);
+        free_build_tree(bt);
+    }
+};
+
+// the device path's working buffers beside PLOC's
+struct CollapseDev {
+    int *flag = nullptr, *at = nullptr, *sub = nullptr, *item = nullptr, *item2 = nullptr, *slots = nullptr;
+    float* v = nullptr;
+    float4* nodes = nullptr;
+    unsigned long long *sums = nullptr, *scan = nullptr, *tot = nullptr;  // tot: pinned
+    void* tmp = nullptr;
+    void release() {
+        if (tot) (void)hipHostFree(tot);
+        for (void* p : {(void*)flag, (void*)at, (void*)sub, (void*)item, (void*)item2, (void*)slots, (void*)v, (void*)nodes,
+                        (void*)sums, (void*)scan, tmp})
+            if (p) (void)hipFree(p);
+        *this = CollapseDev();
+    }
+};
+
+struct RebuildTimes {
+    float ploc = 0.0f, collapse = 0.0f, fill = 0.0f;
+    int launches = 0;
+};
+
+enum { WHY_NONE = 0, WHY_DEEP = 1, WHY_NODES = 2 };
+
+// One view on the device from the coordinates of all n_all triangles. x < 0: the full view; else the subset whose
+// |n|^2 >= x, when it has members and fewer than fewer_than (else out stays empty). area (nullable): += the view's
+// decoded child-box area. why: RT_E_STATE's reason (too deep for the wide walk). Waits for the stream per PLOC round
+// and per wide level; nothing of the context's scene is touched.
+int device_view(rt_ctx* ctx, const float* coords, int n_all, double x, size_t fewer_than, int R, float inflate,
+                double* area, NewView& out, RebuildTimes& tm, int& why, PlocDev& P, CollapseDev& D) {
+    hipStream_t st = ctx->stream;
+    auto t0 = clk::now();
+    int m = n_all;
+    const float* v = coords;
+    HIPC(hipHostMalloc((void**)&D.tot, sizeof(unsigned long long) * 2, hipHostMallocDefault));
+    if (x >= 0.0) {  // a. subset compaction
+        HIPC(hipMalloc((void**)&D.flag, sizeof(int) * n_all));
+        HIPC(hipMalloc((void**)&D.at, sizeof(int) * n_all));
+        size_t bytes = 0;
+        HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, D.flag, D.at, n_all, st));
+        HIPC(hipMalloc(&D.tmp, std::max<size_t>(bytes, 16)));
+        rtc::k_hittable<<<(n_all + 255) / 256, 256, 0, st>>>(coords, n_all, x, D.flag);
+        HIPC(hipGetLastError());
+        HIPC(hipcub::DeviceScan::ExclusiveSum(D.tmp, bytes, D.flag, D.at, n_all, st));
+        int* last = (int*)D.tot;
+        HIPC(hipMemcpyAsync(last, D.flag + n_all - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(last + 1, D.at + n_all - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        m = last[0] + last[1];
+        tm.launches += 4;
+        if (m <= 0 || (size_t)m >= fewer_than) return RT_OK;
+        HIPC(hipMalloc((void**)&D.sub, sizeof(int) * m));
+        HIPC(hipMalloc((void**)&D.v, sizeof(float) * 9 * (size_t)m));
+        rtc::k_gather<<<(n_all + 255) / 256, 256, 0, st>>>(coords, n_all, D.flag, D.at, D.sub, D.v);
+        HIPC(hipGetLastError());
+        tm.launches++;
+        v = D.v;
+        (void)hipFree(D.tmp);  // (the scan over the level's nodes below sizes its own)
+        D.tmp = nullptr;
+    }
+    // b. PLOC from the device vertices
+    int rc;
+    if ((rc = ploc_alloc(ctx, P, m))) return rc;
+    if ((rc = ploc_build(ctx, P, v, R))) {
+        if (rc == RT_E_STATE) ctx->err = "rt_rebuild_views: the device build made no progress";
+        return rc;
+    }
+    tm.launches += 5 + 10 * P.rounds;
+    tm.ploc += ms_since(t0);
+    t0 = clk::now();
+    // c, d. the greedy collapse, one launch pair and one scan per wide level
+    const int cap = m;  // wide nodes are distinct binary nodes of more than 4 triangles, or the root
+    HIPC(hipMalloc((void**)&D.nodes, sizeof(float4) * 5 * (size_t)cap));
+    HIPC(hipMalloc((void**)&D.item, sizeof(int) * cap));
+    HIPC(hipMalloc((void**)&D.item2, sizeof(int) * cap));
+    HIPC(hipMalloc((void**)&D.slots, sizeof(int) * 8 * (size_t)cap));
+    HIPC(hipMalloc((void**)&D.sums, sizeof(unsigned long long) * cap));
+    HIPC(hipMalloc((void**)&D.scan, sizeof(unsigned long long) * cap));
+    HIPC(hipMalloc((void**)&out.w.orig, sizeof(int) * m));
+    size_t scan_bytes = 0;
+    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, D.sums, D.scan, cap, st));
+    HIPC(hipMalloc(&D.tmp, std::max<size_t>(scan_bytes, 16)));
+    HIPC(hipMemcpyAsync(D.item, P.C, sizeof(int), hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(&out.bt.root, P.C, sizeof(int), hipMemcpyDeviceToHost, st));
+    const rtc::DevTree tree{P.left, P.right, P.cnt, P.nlo, P.nhi, m};
+    int first = 0, count = 1;
+    long long tri_first = 0;
+    out.t.off = {0};
+    while (count > 0) {
+        if ((long long)first + count > cap) {
+            ctx->err = "rt_rebuild_views: the collapse made more wide nodes than binary nodes";
+            return RT_E_STATE;
+        }
+        if ((int)out.t.off.size() > rtd::WSTACK) {
+            ctx->err = "rt_rebuild_views: the device tree is too deep for the wide walk";
+            why = WHY_DEEP;
+            return RT_E_STATE;
+        }
+        const int g = (count + 63) / 64;
+        rtc::k_collapse<<<g, 64, 0, st>>>(tree, D.item, count, D.slots, D.sums);
+        HIPC(hipGetLastError());
+        size_t b = scan_bytes;
+        HIPC(hipcub::DeviceScan::ExclusiveSum(D.tmp, b, D.sums, D.scan, count, st));
+        HIPC(hipMemcpyAsync(D.tot, D.sums + count - 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(D.tot + 1, D.scan + count - 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        rtc::k_emit<<<g, 64, 0, st>>>(tree, D.slots, D.scan, first, count, first + count, (int)tri_first, P.sorted, D.sub,
+                                      D.nodes, D.item2, out.w.orig);
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(st));
+        tm.launches += 5;
+        const unsigned long long total = D.tot[0] + D.tot[1];
+        first += count;
+        out.t.off.push_back(first);
+        count = (int)(total >> 32);
+        tri_first += (long long)(total & 0xFFFFFFFFull);
+        std::swap(D.item, D.item2);
+        if (tri_first > m) break;
+    }
+    if (tri_first != m) {
+        ctx->err = "rt_rebuild_views: the collapse did not place every triangle once";
+        return RT_E_STATE;
+    }
+    const int n_wide = first;
+    tm.collapse += ms_since(t0);
+    t0 = clk::now();
+    // e. the view's own buffers and the refit's fill: records, then boxes level by level, deepest first
+    HIPC(hipMalloc((void**)&out.w.nodes, sizeof(float4) * 5 * (size_t)n_wide));
+    HIPC(hipMalloc((void**)&out.w.tris, sizeof(float4) * 3 * (size_t)m));
+    HIPC(hipMalloc((void**)&out.t.d_exact, sizeof(float4) * 2 * (size_t)n_wide));
+    HIPC(hipMemcpyAsync(out.w.nodes, D.nodes, sizeof(float4) * 5 * (size_t)n_wide, hipMemcpyDeviceToDevice, st));
+    out.w.n = n_wide;
+    out.w.depth = (int)out.t.off.size() - 1;
+    out.w.tris_n = m;
+    out.t.made = true;
+    int rf;
+    if ((rf = refit_wide(ctx, out.w, out.t, coords, inflate, area))) return rf;
+    tm.launches += 2 + out.w.depth;
+    if (x >= 0.0) {  // a subset view's membership bitmap (make_wide_topo's)
+        const size_t words = ((size_t)n_all + 31) / 32;
+        HIPC(hipMalloc((void**)&out.t.d_bits, sizeof(unsigned) * words));
+        HIPC(hipMemsetAsync(out.t.d_bits, 0, sizeof(unsigned) * words, st));
+        rtr::k_member<<<(m + 255) / 256, 256, 0, st>>>(out.w.orig, m, out.t.d_bits);
+        HIPC(hipGetLastError());
+        tm.launches += 2;
+    }
+    // the collapsed tree, kept for the test read-back: PLOC's child arrays as they are, the leaves' scene triangles
+    HIPC(hipMalloc((void**)&out.bt.leaf, sizeof(int) * m));
+    rtc::k_leaf_ids<<<(m + 255) / 256, 256, 0, st>>>(P.sorted, D.sub, m, out.bt.leaf);
+    HIPC(hipGetLastError());
+    out.bt.left = P.left;
+    out.bt.right = P.right;
+    P.left = P.right = nullptr;
+    out.bt.n = m;
+    HIPC(hipStreamSynchronize(st));  // (the working buffers are freed by the caller)
+    tm.fill += ms_since(t0);
+    return RT_OK;
+}
+
+// the new coordinates as host triangles (the builds read coords and centroid)
+int download_triangles(rt_ctx* ctx, const float* coords, int n, std::vector<rt_triangle>& T) {
+    std::vector<float> hv(9 * (size_t)n);
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMemcpy(hv.data(), coords, sizeof(float) * hv.size(), hipMemcpyDeviceToHost));
+    T.resize((size_t)n);
+    const rt_vec3 zero{0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < n; i++) {
+        const float* p = &hv[9 * (size_t)i];
+        const rt_vec3 a{p[0], p[1], p[2]}, b{p[3], p[4], p[5]}, c{p[6], p[7], p[8]};
+        rth_triangle_init(&T[i], &a, &b, &c, &zero, &zero, &zero);
+    }
+    return RT_OK;
+}
+
+// the three views through the upload's own path (wide_view / subset_view) over downloaded coordinates
+int host_views(rt_ctx* ctx, const float* coords, int n, float inflate, NewView nv[3], RebuildTimes& tm) {
+    std::vector<rt_triangle> T;
+    int rc = download_triangles(ctx, coords, n, T);
+    if (rc) return rc;
+    const float keep[3] = {ctx->t_ploc, ctx->t_treelet, ctx->t_collapse};  // (the upload's stage times stay its own)
+    ctx->t_ploc = ctx->t_treelet = ctx->t_collapse = 0.0f;
+    rt_scene s2{};
+    s2.triangles = T.data();
+    s2.n_triangles = n;
+    s2.ploc_radius = ctx->ploc_radius;
+    s2.collapse_node_cost = ctx->collapse_cost;
+    const int R = ctx->ploc_radius > 0 ? std::min(ctx->ploc_radius, rtb::PLOC_R_MAX) : rtb::PLOC_R;
+    HostWide hw[3];
+    int built = ctx->built_accel;
+    rc = wide_view(ctx, T.data(), n, built, R, inflate, ctx->collapse_cost, hw[0]);
+    if (rc == RT_E_STATE && built == RT_ACCEL_GPU) {  // too deep for the wide walk: the host build, as the upload does
+        built = RT_ACCEL_HOST;
+        hw[0] = HostWide();
+        rc = wide_view(ctx, T.data(), n, built, R, inflate, ctx->collapse_cost, hw[0]);
+    }
+    if (rc == RT_E_STATE) ctx->err = "rt_rebuild_views: no wide view could be built over the new coordinates";
+    if (!rc) rc = subset_view(ctx, &s2, 1.0, (size_t)n, built, inflate, hw[1]);
+    if (!rc) rc = subset_view(ctx, &s2, PRIMARY_D, (size_t)n - (size_t)n / 50, built, inflate, hw[2]);
+    tm.ploc = ctx->t_ploc + ctx->t_treelet;
+    tm.collapse = ctx->t_collapse;
+    ctx->t_ploc = keep[0];
+    ctx->t_treelet = keep[1];
+    ctx->t_collapse = keep[2];
+    if (rc) return rc;
+    const auto t0 = clk::now();
+    for (int k = 0; k < 3; k++)
+        if ((rc = upload_wide(ctx, hw[k], nv[k].w))) return rc;
+    tm.fill = ms_since(t0);
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_rebuild_views(rt_ctx* ctx, const rt_view_rebuild* r) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_rebuild_views: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !r->coords) return arg_err(ctx, "rt_rebuild_views: null rebuild / coords");
+    if (r->mode < RT_REBUILD_AUTO || r->mode > RT_REBUILD_HOST) return arg_err(ctx, "rt_rebuild_views: bad mode");
+    if (r->n_triangles != ctx->n_tris) return arg_err(ctx, "rt_rebuild_views: n_triangles differs from the uploaded scene's");
+    if (!ctx->wide.nodes) {
+        ctx->err = "rt_rebuild_views: the scene has no wide view (RT_ACCEL_REFERENCE)";
+        return RT_E_STATE;
+    }
+    if (r->mode == RT_REBUILD_DEVICE && ctx->built_accel != RT_ACCEL_GPU)
+        return arg_err(ctx, "rt_rebuild_views: RT_REBUILD_DEVICE needs a scene built with RT_ACCEL_GPU");
+    HIPC(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const auto t_call = clk::now();
+    if (!ctx->r_ev0) HIPC(hipEventCreate(&ctx->r_ev0));
+    if (!ctx->r_ev1) HIPC(hipEventCreate(&ctx->r_ev1));
+    if (!ctx->r_evs) HIPC(hipEventCreate(&ctx->r_evs));
+    HIPC(hipEventRecord(ctx->r_evs, st));  // (becomes r_ev0 only when the rebuild is made)
+    // 1. the whole vertex update
+    const rt_vertex_update u{r->coords, r->n_triangles};
+    float inflate = 0.0f;
+    int rc = update_vertices(ctx, &u, false, &inflate);
+    if (rc) return rc;
+    const int n = ctx->n_tris;
+    // 2. the new views into fresh buffers
+    NewView nv[3];
+    RebuildTimes tm;
+    rt_rebuild_info ri{};
+    bool device = r->mode == RT_REBUILD_DEVICE || (r->mode == RT_REBUILD_AUTO && ctx->built_accel == RT_ACCEL_GPU);
+    auto drop = [&]() {
+        for (NewView& v : nv) v.release();
+    };
+    HIPC(hipMemsetAsync(ctx->d_area + 4, 0, sizeof(double), st));
+    if (device) {
+        const int R = ctx->ploc_radius > 0 ? std::min(ctx->ploc_radius, rtb::PLOC_R_MAX) : rtb::PLOC_R;
+        const double xs[3] = {-1.0, sqrt_threshold(UNIT_KEEP * (double)rtd::EPS / 1.0),
+                              sqrt_threshold(UNIT_KEEP * (double)rtd::EPS / PRIMARY_D)};
+        const size_t fewer[3] = {0, (size_t)n, (size_t)n - (size_t)n / 50};
+        int why = WHY_NONE;
+        for (int k = 0; k < 3 && !rc; k++) {
+            PlocDev P;
+            CollapseDev D;
+            rc = device_view(ctx, r->coords, n, xs[k], fewer[k], R, inflate, k == 0 ? ctx->d_area + 4 : nullptr, nv[k],
+                             tm, why, P, D);
+            if (rc) (void)hipStreamSynchronize(st);
+            P.release();
+            D.release();
+            if (!rc && nv[k].w.n > rtd::WIDE_MAX_NODES && r->mode == RT_REBUILD_AUTO) {
+                rc = RT_E_STATE;
+                why = WHY_NODES;
+            }
+        }
+        if (rc == RT_E_STATE && why != WHY_NONE && r->mode == RT_REBUILD_AUTO) {  // the fallback
+            drop();
+            tm = RebuildTimes();
+            ri.fell_back = why;
+            device = false;
+            rc = RT_OK;
+            HIPC(hipMemsetAsync(ctx->d_area + 4, 0, sizeof(double), st));
+        }
+    }
+    if (!rc && !device) {
+        rc = host_views(ctx, r->coords, n, inflate, nv, tm);
+        if (!rc) {
+            rtr::k_wide_area<<<(nv[0].w.n + 255) / 256, 256, 0, st>>>(nv[0].w.nodes, nv[0].w.n, ctx->d_area + 4);
+            if (hipGetLastError() != hipSuccess) rc = RT_E_HIP;
+        }
+    }
+    if (rc || !nv[0].w.nodes) {  // the refitted scene stays
+        drop();
+        return rc ? rc : RT_E_STATE;
+    }
+    // 3, 4. swap the views in (stream order: everything issued so far has run) and free the old ones with their topologies
+    HIPC(hipStreamSynchronize(st));
+    DevWide* views[3] = {&ctx->wide, &ctx->unit, &ctx->prim};
+    RefitTopo* topos[3] = {&ctx->tp_wide, &ctx->tp_unit, &ctx->tp_prim};
+    for (int k = 0; k < 3; k++) {
+        free_wide(*views[k]);
+        free_topo(*topos[k]);
+        free_build_tree(ctx->bt[k]);
+        *views[k] = nv[k].w;
+        *topos[k] = nv[k].t;
+        ctx->bt[k] = nv[k].bt;
+        ri.nodes[k] = nv[k].w.n;
+        ri.depth[k] = nv[k].w.depth;
+        ri.views_built += nv[k].w.nodes != nullptr;
+    }
+    // 5. the next area_ratio is measured against the rebuilt view ([3]: the area before, [0] = [1] = [2]: the area after)
+    HIPC(hipMemcpyAsync(ctx->d_area + 3, ctx->d_area + 1, sizeof(double), hipMemcpyDeviceToDevice, st));
+    for (int k = 0; k < 3; k++)
+        HIPC(hipMemcpyAsync(ctx->d_area + k, ctx->d_area + 4, sizeof(double), hipMemcpyDeviceToDevice, st));
+    ctx->area_base = true;
+    // 6, 7. the packed layouts' bound and the scene report
+    ctx->pk_ok = std::max(ctx->wide.n, std::max(ctx->unit.n, ctx->prim.n)) <= rtd::WIDE_MAX_NODES &&
+                 !(ctx->flags & RT_FLAG_UNPACKED_STACK);
+    ctx->info.wide_nodes = ctx->wide.n;
+    ctx->info.wide_depth = ctx->wide.depth;
+    ctx->info.unit_triangles = ctx->unit.tris_n;
+    ctx->info.unit_nodes = ctx->unit.n;
+    ctx->info.unit_depth = ctx->unit.depth;
+    ctx->info.primary_triangles = ctx->prim.tris_n;
+    ctx->info.primary_nodes = ctx->prim.n;
+    std::swap(ctx->r_ev0, ctx->r_evs);
+    HIPC(hipEventRecord(ctx->r_ev1, st));
+    ri.mode_used = device ? RT_REBUILD_DEVICE : RT_REBUILD_HOST;
+    ri.launches = tm.launches;
+    ri.ploc_ms = tm.ploc;
+    ri.collapse_ms = tm.collapse;
+    ri.fill_ms = tm.fill;
+    ri.host_ms = ms_since(t_call);
+    ctx->rinfo = ri;
+    ctx->rebuilt = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_rebuild_info(rt_ctx* ctx, rt_rebuild_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->rebuilt) {
+        ctx->err = "rt_get_rebuild_info: no view rebuild made";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    *info = ctx->rinfo;
+    double a[2] = {0.0, 0.0};
+    HIPC(hipMemcpy(a, ctx->d_area + 2, sizeof a, hipMemcpyDeviceToHost));
+    info->area_after = a[0];
+    info->area_before = a[1];
+    HIPC(hipEventElapsedTime(&info->rebuild_ms, ctx->r_ev0, ctx->r_ev1));
+    return RT_OK;
+}
+
+extern "C" int rt_debug_read_build_tree(rt_ctx* ctx, int view, int* left, int* right, int* leaf_tri, int cap, int* root) {
+    if (!ctx || view < 0 || view > 2 || cap < 0) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_debug_read_build_tree: no scene uploaded";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    const rt_ctx::BuildTree& b = ctx->bt[view];
+    if (!b.leaf) return 0;
+    const int nl = std::min(b.n, cap), ni = std::min(b.n - 1, cap);
+    if (leaf_tri && nl > 0) HIPC(hipMemcpy(leaf_tri, b.leaf, sizeof(int) * (size_t)nl, hipMemcpyDeviceToHost));
+    if (left && ni > 0) HIPC(hipMemcpy(left, b.left, sizeof(int) * (size_t)ni, hipMemcpyDeviceToHost));
+    if (right && ni > 0) HIPC(hipMemcpy(right, b.right, sizeof(int) * (size_t)ni, hipMemcpyDeviceToHost));
+    if (root) *root = b.root;
+    return b.n;
 }
 
 // ---------------------------------------------------------------- radiance queries (rt_shade.hpp)
@@ -3477,7 +3922,7 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
         if (p) (void)hipFree(p);
     if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
     if (ctx->h_lights) (void)hipHostFree(ctx->h_lights);
-    for (hipEvent_t e : {ctx->u_ev0, ctx->u_ev1, ctx->u_evs, ctx->lights_ev})
+    for (hipEvent_t e : {ctx->u_ev0, ctx->u_ev1, ctx->u_evs, ctx->lights_ev, ctx->r_ev0, ctx->r_ev1, ctx->r_evs})
         if (e) (void)hipEventDestroy(e);
     if (ctx->d_shq) (void)hipFree(ctx->d_shq);
     if (ctx->s_ev0) (void)hipEventDestroy(ctx->s_ev0);

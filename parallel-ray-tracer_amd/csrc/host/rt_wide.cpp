@@ -28,6 +28,7 @@
 
 #include "rt_host.h"
 #include "../hip/rt_quant.hpp"  // the quantiser the refit shares with the device (rth_wbvh_refit below)
+#include "../hip/rt_collapse.hpp"  // the greedy collapse rule the view rebuild shares with the device (rth_wbvh_build_greedy)
 
 namespace {
 
@@ -601,6 +602,198 @@ extern "C" int rth_wbvh_refit(uint32_t* nodes, int n_nodes, const int* tri_order
         }
         exact[k] = own;
         rtq::requantise(W, box, inflate);
+    }
+    return RT_OK;
+}
+
+// ---- the greedy collapse (rt_collapse.hpp): the CPU mirror of the device's view rebuild
+
+namespace {
+// WBuilder's binary tree through the shared rule's accessor
+struct HostTree {
+    const std::vector<BNode>& bn;
+    bool interior(int i) const { return bn[i].l >= 0; }
+    int left(int i) const { return bn[i].l; }
+    int right(int i) const { return bn[i].r; }
+    int count(int i) const { return bn[i].cnt; }
+    void box(int i, float* lo, float* hi) const {
+        for (int a = 0; a < 3; a++) {
+            lo[a] = bn[i].b.lo[a];
+            hi[a] = bn[i].b.hi[a];
+        }
+    }
+};
+}  // namespace
+
+extern "C" int rth_wbvh_build_greedy(const rt_bvh_node* bvh, int n_nodes, const int* tri_idx, const rt_triangle* tris,
+                                     int n_tris, float inflate, uint32_t** nodes_out, int** tri_order_out,
+                                     rth_wbvh_info* info) {
+    if (!bvh || n_nodes <= 0 || !tri_idx || !tris || n_tris <= 0 || !nodes_out || !tri_order_out ||
+        !(inflate >= 0.0f))
+        return RT_E_ARG;
+    WBuilder w;
+    w.T = tris;
+    w.n = n_tris;
+    w.inflate = inflate;
+    w.idx.assign(tri_idx, tri_idx + n_tris);
+    std::vector<char> named((size_t)n_tris, 0);
+    for (int t : w.idx) {
+        if (t < 0 || t >= n_tris || named[t]) return RT_E_ARG;  // (not a permutation)
+        named[t] = 1;
+    }
+    w.bn.reserve(2 * (size_t)n_tris + 2);
+    bool bad = false;
+    const int root = w.make(w.bn, bvh, n_nodes, 0, 0, bad);
+    if (bad || root < 0) return RT_E_ARG;
+    for (const BNode& b : w.bn)
+        if (b.cnt <= 0) return RT_E_ARG;  // a subtree whose triangles are not one range of tri_idx
+    const HostTree tree{w.bn};
+    // level by level, as the device does: every node's children and slots by the shared rule, the level's child and
+    // triangle bases by running sums in node order
+    std::vector<int> level{root}, nxt;
+    std::vector<uint32_t> words;
+    std::vector<int> order((size_t)n_tris, -1);
+    size_t n_wide = 0, n_order = 0;
+    int depth = 0, max_kids = 0;
+    while (!level.empty()) {
+        depth++;
+        size_t next_node = n_wide + level.size();
+        words.resize(20 * next_node);
+        nxt.clear();
+        for (size_t i = 0; i < level.size(); i++) {
+            int kid[rtc::WIDTH], slot_kid[rtc::WIDTH];
+            const int k = rtc::collapse(tree, level[i], kid);
+            rtc::assign_slots(tree, kid, k, slot_kid);
+            max_kids = std::max(max_kids, k);
+            uint32_t imask = 0;
+            uint8_t meta[rtc::WIDTH] = {0};
+            const size_t cbase = next_node, tbase = n_order;
+            int off = 0;
+            for (int s = 0; s < rtc::WIDTH; s++) {
+                if (slot_kid[s] < 0) continue;
+                const BNode& c = w.bn[kid[slot_kid[s]]];
+                if (c.cnt > rtc::LEAF_MAX) {
+                    imask |= 1u << s;
+                    nxt.push_back(kid[slot_kid[s]]);
+                    next_node++;
+                    continue;
+                }
+                if (n_order + (size_t)c.cnt > (size_t)n_tris) return RT_E_ARG;  // a triangle referenced twice
+                meta[s] = (uint8_t)((c.cnt << 5) | off);
+                for (int t = c.first; t < c.first + c.cnt; t++) order[n_order++] = w.idx[t];
+                off += c.cnt;
+            }
+            rtc::topology_words(&words[20 * (n_wide + i)], imask, (uint32_t)cbase, (uint32_t)tbase, meta);
+        }
+        n_wide += level.size();
+        level.swap(nxt);
+    }
+    if (n_order != (size_t)n_tris) return RT_E_ARG;  // a triangle referenced twice or never
+    // the boxes: the shared quantiser over the new topology (what a refit with unmoved triangles reproduces)
+    const int rc = rth_wbvh_refit(words.data(), (int)n_wide, order.data(), tris, n_tris, inflate);
+    if (rc != RT_OK) return rc;
+    uint32_t* nodes = (uint32_t*)std::malloc(sizeof(uint32_t) * words.size());
+    int* ord = (int*)std::malloc(sizeof(int) * order.size());
+    if (!nodes || !ord) {
+        std::free(nodes);
+        std::free(ord);
+        return RT_E_NOMEM;
+    }
+    std::memcpy(nodes, words.data(), sizeof(uint32_t) * words.size());
+    std::memcpy(ord, order.data(), sizeof(int) * order.size());
+    *nodes_out = nodes;
+    *tri_order_out = ord;
+    if (info) {
+        info->n_nodes = (int)n_wide;
+        info->n_tris = n_tris;
+        info->depth = depth;
+        info->max_children = max_kids;
+    }
+    return RT_OK;
+}
+
+// ---- structural validator of a wide tree's words
+
+extern "C" int rth_wbvh_check(const uint32_t* nodes, int n_nodes, const int* tri_order, int n_tris, int max_depth,
+                              rth_wbvh_info* info) {
+    if (!nodes || n_nodes <= 0 || !tri_order || n_tris <= 0) return RT_E_ARG;
+    int max_kids = 0;
+    // 1. every leaf slot holds 1..4 triangles
+    for (int k = 0; k < n_nodes; k++) {
+        const uint32_t* W = nodes + 20 * (size_t)k;
+        int kids = 0;
+        for (int s = 0; s < rtq::WIDTH; s++) {
+            const uint32_t m = rtq::meta_of(W, s);
+            const bool inner = (rtq::imask_of(W) >> s) & 1u;
+            if (inner ? m != 0 : (m != 0 && ((m >> 5) < 1 || (m >> 5) > (uint32_t)LEAF_MAX))) return RTH_WCHK_LEAF;
+            kids += inner || m != 0;
+        }
+        max_kids = std::max(max_kids, kids);
+    }
+    // 2. every child index and triangle range in bounds
+    for (int k = 0; k < n_nodes; k++) {
+        const uint32_t* W = nodes + 20 * (size_t)k;
+        const int inner = __builtin_popcount(rtq::imask_of(W));
+        if (inner && ((uint64_t)W[4] + (uint64_t)inner > (uint64_t)n_nodes || W[4] == 0)) return RTH_WCHK_RANGE;
+        for (int s = 0; s < rtq::WIDTH; s++) {
+            const uint32_t m = rtq::meta_of(W, s);
+            if (m && (uint64_t)W[5] + (m & 31u) + (m >> 5) > (uint64_t)n_tris) return RTH_WCHK_RANGE;
+        }
+    }
+    // 3. every node but the root has exactly one parent
+    std::vector<int> parents((size_t)n_nodes, 0);
+    for (int k = 0; k < n_nodes; k++) {
+        const uint32_t* W = nodes + 20 * (size_t)k;
+        const int inner = __builtin_popcount(rtq::imask_of(W));
+        for (int j = 0; j < inner; j++) parents[W[4] + (uint32_t)j]++;
+    }
+    if (parents[0] != 0) return RTH_WCHK_PARENT;
+    for (int k = 1; k < n_nodes; k++)
+        if (parents[k] != 1) return RTH_WCHK_PARENT;
+    // 4. levels are contiguous breadth-first ranges: a level's children, in node order, are the next range
+    int depth = 0;
+    for (int s = 0, e = 1; s < e;) {
+        depth++;
+        long long next = e;
+        for (int k = s; k < e; k++) {
+            const uint32_t* W = nodes + 20 * (size_t)k;
+            const int inner = __builtin_popcount(rtq::imask_of(W));
+            if (inner && (long long)W[4] != next) return RTH_WCHK_LEVELS;
+            next += inner;
+        }
+        s = e;
+        e = (int)next;
+        if (s == e && e != n_nodes) return RTH_WCHK_LEVELS;
+    }
+    // 5. every wide-leaf position is covered exactly once
+    std::vector<char> seen((size_t)n_tris, 0);
+    for (int k = 0; k < n_nodes; k++) {
+        const uint32_t* W = nodes + 20 * (size_t)k;
+        for (int s = 0; s < rtq::WIDTH; s++) {
+            const uint32_t m = rtq::meta_of(W, s);
+            for (uint32_t j = 0; j < (m >> 5); j++) {
+                char& c = seen[W[5] + (m & 31u) + j];
+                if (c) return RTH_WCHK_COVER;
+                c = 1;
+            }
+        }
+    }
+    for (char c : seen)
+        if (!c) return RTH_WCHK_COVER;
+    // 6. tri_order is injective (a permutation of 0 .. n_tris - 1)
+    std::fill(seen.begin(), seen.end(), 0);
+    for (int i = 0; i < n_tris; i++) {
+        const int t = tri_order[i];
+        if (t < 0 || t >= n_tris || seen[t]) return RTH_WCHK_ORDER;
+        seen[t] = 1;
+    }
+    // 7. depth
+    if (max_depth > 0 && depth > max_depth) return RTH_WCHK_DEPTH;
+    if (info) {
+        info->n_nodes = n_nodes;
+        info->n_tris = n_tris;
+        info->depth = depth;
+        info->max_children = max_kids;
     }
     return RT_OK;
 }

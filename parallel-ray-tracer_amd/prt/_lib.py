@@ -145,6 +145,22 @@ class UpdateInfo(ctypes.Structure):  # rt_update_info
                 ("update_ms", ctypes.c_float)]
 
 
+class ViewRebuild(ctypes.Structure):  # rt_view_rebuild
+    _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+class RebuildInfo(ctypes.Structure):  # rt_rebuild_info
+    _fields_ = [("mode_used", ctypes.c_int), ("fell_back", ctypes.c_int), ("views_built", ctypes.c_int),
+                ("nodes", ctypes.c_int * 3), ("depth", ctypes.c_int * 3), ("launches", ctypes.c_int),
+                ("area_before", ctypes.c_double), ("area_after", ctypes.c_double), ("rebuild_ms", ctypes.c_float),
+                ("host_ms", ctypes.c_float), ("ploc_ms", ctypes.c_float), ("collapse_ms", ctypes.c_float),
+                ("fill_ms", ctypes.c_float)]
+
+
+REBUILD_MODES = {"auto": 0, "device": 1, "host": 2}
+# rth_wbvh_check's codes (include/rt_host.h RTH_WCHK_*)
+WCHK = {"leaf": -101, "range": -102, "parent": -103, "levels": -104, "cover": -105, "order": -106, "depth": -107}
+
 _host = None
 _hip = None
 
@@ -179,6 +195,9 @@ def host():
                                      ctypes.c_float, P(P(ctypes.c_uint32)), P(P(ctypes.c_int)), P(WbvhInfo)]
         L.rth_wbvh_refit.argtypes = [P(ctypes.c_uint32), ctypes.c_int, P(ctypes.c_int), P(Triangle), ctypes.c_int,
                                      ctypes.c_float]
+        L.rth_wbvh_build_greedy.argtypes = L.rth_wbvh_build.argtypes
+        L.rth_wbvh_check.argtypes = [P(ctypes.c_uint32), ctypes.c_int, P(ctypes.c_int), ctypes.c_int, ctypes.c_int,
+                                     P(WbvhInfo)]
         L.rth_triangle_init.argtypes = [P(Triangle), P(Vec3), P(Vec3), P(Vec3), P(Vec3), P(Vec3), P(Vec3)]
         L.rth_triangle_init.restype = None
         L.rth_triangles_load_cached.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
@@ -240,6 +259,10 @@ def hip():
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]
         L.rt_debug_read_wide.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_int]
+        L.rt_rebuild_views.argtypes = [ctypes.c_void_p, P(ViewRebuild)]
+        L.rt_get_rebuild_info.argtypes = [ctypes.c_void_p, P(RebuildInfo)]
+        L.rt_debug_read_build_tree.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int, P(ctypes.c_int)]
         L.rt_device_count.argtypes = []
         L.rt_version.restype = ctypes.c_char_p
         _hip = L

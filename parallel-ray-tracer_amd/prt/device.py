@@ -462,6 +462,52 @@ class Renderer:
         self._chk(_L.rt_get_update_info(self._ctx, ctypes.byref(i)), "rt_get_update_info")
         return {f: getattr(i, f) for f, _ in _lib.UpdateInfo._fields_}
 
+    def rebuild_views(self, coords, mode="auto"):
+        """rt_rebuild_views: update_vertices(coords), then new topologies for the fast walk's wide views (full, unit,
+        primary) built over those coordinates -- after large motion, when update_info()["area_ratio"] has grown. The
+        reference tree stays, so every render and query returns the bits it returns after update_vertices(coords).
+        mode: "device" (PLOC and the greedy collapse on the GPU; GPU-built scenes only), "host" (the upload's own build
+        over downloaded coordinates) or "auto"."""
+        import torch
+        if not isinstance(coords, torch.Tensor):
+            raise RtError(f"coords: expected a torch tensor, got {type(coords).__name__}")
+        if coords.dim() != 3 or tuple(coords.shape[1:]) != (3, 3):
+            raise RtError(f"coords: shape {tuple(coords.shape)}, expected [n, 3, 3]")
+        if mode not in _lib.REBUILD_MODES:
+            raise RtError(f"mode: {mode!r}, expected one of {sorted(_lib.REBUILD_MODES)}")
+        n = coords.shape[0]
+        u = _lib.ViewRebuild(_ptr(coords, "coords", 9 * n, (torch.float32,), self.device), n, _lib.REBUILD_MODES[mode])
+        self._chk(_L.rt_rebuild_views(self._ctx, ctypes.byref(u)), "rt_rebuild_views")
+
+    def rebuild_info(self):
+        """rt_get_rebuild_info: what the last rebuild_views did (mode_used, fell_back, views_built, nodes / depth per
+        view, the full view's area_before / area_after, rebuild_ms, host_ms and the stages' times); synchronises"""
+        i = _lib.RebuildInfo()
+        self._chk(_L.rt_get_rebuild_info(self._ctx, ctypes.byref(i)), "rt_get_rebuild_info")
+        d = {f: getattr(i, f) for f, _ in _lib.RebuildInfo._fields_}
+        d["nodes"], d["depth"] = list(i.nodes), list(i.depth)
+        d["mode_used"] = {v: k for k, v in _lib.REBUILD_MODES.items()}[i.mode_used]
+        return d
+
+    def _debug_build_tree(self, view="full"):
+        """test-only (rt_debug_read_build_tree): the binary tree the last device rebuild collapsed for a view ->
+        (left, right, leaf_tri, root): nodes 0 .. n - 1 are leaves, leaf k holding scene triangle leaf_tri[k]; node
+        n + j has the children left[j] and right[j]; or None without such a tree; synchronises"""
+        v = {"full": 0, "unit": 1, "primary": 2}[view]
+        root = ctypes.c_int()
+        n = _L.rt_debug_read_build_tree(self._ctx, v, None, None, None, 0, ctypes.byref(root))
+        if n < 0:
+            self._chk(n, "rt_debug_read_build_tree")
+        if n == 0:
+            return None
+        left, right = np.zeros(max(n - 1, 1), np.int32), np.zeros(max(n - 1, 1), np.int32)
+        leaf = np.zeros(n, np.int32)
+        got = _L.rt_debug_read_build_tree(self._ctx, v, left.ctypes.data, right.ctypes.data, leaf.ctypes.data, n,
+                                          ctypes.byref(root))
+        if got < 0:
+            self._chk(got, "rt_debug_read_build_tree")
+        return left[:n - 1], right[:n - 1], leaf, root.value
+
     def update_lights(self, lights):
         """rt_update_lights: new positions / colours for the uploaded lights (a LIGHT_DTYPE array of the same length)"""
         from .host import LIGHT_DTYPE

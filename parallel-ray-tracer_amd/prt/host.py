@@ -120,7 +120,7 @@ def bvh_build(tris, heuristic=3, rng=None):
     return nodes_np, idx_np, stats
 
 
-def wbvh_build(nodes, tri_idx, tris, inflate=0.0):
+def wbvh_build(nodes, tri_idx, tris, inflate=0.0, _fn="rth_wbvh_build"):
     """the fast walk's 8-wide quantised BVH (rth_wbvh_build, rt_wide.cpp) from a reference-layout BVH
     -> (words uint32 [n_nodes, 20], tri_order int32 [n], info dict)"""
     L = _lib.host()
@@ -130,12 +130,53 @@ def wbvh_build(nodes, tri_idx, tris, inflate=0.0):
     words = P(ctypes.c_uint32)()
     order = P(ctypes.c_int)()
     info = _lib.WbvhInfo()
-    _check(L.rth_wbvh_build(nodes.ctypes.data_as(P(_lib.BvhNode)), len(nodes), tri_idx.ctypes.data_as(P(ctypes.c_int)),
-                            tris.ctypes.data_as(P(Triangle)), len(tris), float(inflate), ctypes.byref(words),
-                            ctypes.byref(order), ctypes.byref(info)), "wbvh_build")
+    _check(getattr(L, _fn)(nodes.ctypes.data_as(P(_lib.BvhNode)), len(nodes), tri_idx.ctypes.data_as(P(ctypes.c_int)),
+                           tris.ctypes.data_as(P(Triangle)), len(tris), float(inflate), ctypes.byref(words),
+                           ctypes.byref(order), ctypes.byref(info)), _fn[4:])
     w = _take(words, 20 * info.n_nodes, np.dtype(np.uint32)).reshape(-1, 20)
     o = _take(order, info.n_tris, np.dtype(np.int32))
     return w, o, {"n_nodes": info.n_nodes, "depth": info.depth, "max_children": info.max_children}
+
+
+def wbvh_build_greedy(nodes, tri_idx, tris, inflate=0.0):
+    """rth_wbvh_build_greedy: the greedy largest-area collapse the device's view rebuild runs (rt_collapse.hpp), on the
+    host -- same inputs and outputs as wbvh_build; the CPU mirror of Renderer.rebuild_views(mode="device")"""
+    return wbvh_build(nodes, tri_idx, tris, inflate, _fn="rth_wbvh_build_greedy")
+
+
+def wbvh_check(words, tri_order, max_depth=0):
+    """rth_wbvh_check: the structural validator of a wide tree -> (code, info dict); code 0, or _lib.WCHK's code of
+    the first violated property (children and triangle ranges in bounds, one parent per node, breadth-first levels,
+    leaf slots of 1..4 triangles, every position covered once, tri_order injective, depth <= max_depth)"""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    o = np.ascontiguousarray(tri_order, dtype=np.int32)
+    info = _lib.WbvhInfo()
+    rc = _lib.host().rth_wbvh_check(w.ctypes.data_as(P(ctypes.c_uint32)), len(w), o.ctypes.data_as(P(ctypes.c_int)),
+                                    len(o), int(max_depth), ctypes.byref(info))
+    return rc, {"n_nodes": info.n_nodes, "depth": info.depth, "max_children": info.max_children}
+
+
+def bvh_from_links(left, right, root, n):
+    """a binary tree given by child links (nodes 0 .. n - 1: leaves of one triangle each, node n + j: children left[j]
+    and right[j]; Renderer._debug_build_tree's layout) in the reference layout: children at child and child + 1, the
+    leaves numbered depth first, left first -> (nodes NODE_DTYPE (boxes zero: the wide builders take them from the
+    triangles), leaf_order int32 [n]: the leaf at each depth-first position)"""
+    nodes = np.zeros(max(2 * n - 1, 1), NODE_DTYPE)
+    order = np.zeros(n, np.int32)
+    stack, used, pos = [(int(root), 0)], 1, 0
+    while stack:
+        b, at = stack.pop()
+        if b < n:
+            nodes["tr_len"][at], nodes["child"][at] = 1, pos
+            order[pos] = b
+            pos += 1
+        else:
+            nodes["child"][at] = used
+            stack.append((int(right[b - n]), used + 1))
+            stack.append((int(left[b - n]), used))
+            used += 2
+    assert pos == n and used == len(nodes)
+    return nodes, order
 
 
 def wbvh_refit(words, tri_order, tris, inflate=0.0):

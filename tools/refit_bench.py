@@ -16,7 +16,15 @@ one JSON line with
                     differs from the kept one's and exact ties may fall the other way (rt_hip.h); the bit-for-bit
                     comparison with a fresh upload of the kept topology is tests/test_gpu_refit.py's
 and the library's md5.
-usage: python tools/refit_bench.py [--scenes dragon sportscar two_cars car_boxed] [--width 1920 --height 1080]
+--rebuild: view rebuilds instead (rt_rebuild_views), for the `large` motion: four renderers of the same
+moved scene -- refitted (update_vertices), rebuilt on the device, rebuilt on the host, and the fresh upload -- with
+  frame_ms_{refit,device,host,fresh}   kernel time per frame as above, the four sides taken in turn, twice
+  rebuild_{device,host}                that mode's rt_rebuild_info: rebuild_ms (HIP events, the update included), host_ms
+                                       (the call's wall time), the stages, nodes and depth per view, area_before / after
+  ref_build_ms, upload_ms, build_ms    what a fresh upload costs instead
+  frames_to_break_even_{device,host}   rebuild host_ms / (frame_ms_refit - frame_ms_<mode>): frames after which the
+                                       rebuild has paid for itself (null when its frames are not faster)
+usage: python tools/refit_bench.py [--rebuild] [--scenes dragon sportscar two_cars car_boxed] [--width 1920 --height 1080]
        [--runs 7] [--out profiles/<dir>/refit.jsonl]"""
 import argparse
 import json
@@ -57,14 +65,83 @@ def batch_ms(r, cams, W, H, px, runs):
     return statistics.median(ms), min(ms), max(ms), r.launch_info()["variant"]
 
 
+def rebuild_lines(a, emit):
+    import torch
+    from prt import device, host
+    W, H = a.width, a.height
+    md5 = device.lib_md5()
+    cams = [host.camera(W, H)] * FRAMES
+    px = torch.zeros((FRAMES, H, W), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    angle, shift = MOTIONS["large"]
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        coords, tris1 = moved(s.triangles, angle, shift)
+        dc = torch.from_numpy(coords).cuda()
+        sides, info = {}, {}
+        sides["refit"] = device.Renderer(0).upload(s)
+        sides["refit"].update_vertices(dc)
+        area_ratio = sides["refit"].update_info()["area_ratio"]
+        for mode in ("device", "host"):
+            r = sides[mode] = device.Renderer(0).upload(s)
+            times = []
+            for _ in range(max(3, a.runs // 2)):  # (every rebuild starts from the upload's own views)
+                r.upload(s)
+                r.sync()
+                r.rebuild_views(dc, mode=mode)
+                times.append(r.rebuild_info())
+            i = dict(times[-1])
+            for f in ("rebuild_ms", "host_ms", "ploc_ms", "collapse_ms", "fill_ms"):
+                i[f] = round(statistics.median(t[f] for t in times), 3)
+            info[mode] = i
+        t0 = time.perf_counter()
+        s1 = host.Scene(tris1, s.lights)
+        s1.amb = s.amb
+        s1.build_bvh(3)
+        ref_build_ms = (time.perf_counter() - t0) * 1e3
+        sides["fresh"] = device.Renderer(0)
+        t0 = time.perf_counter()
+        sides["fresh"].upload(s1)
+        upload_ms = (time.perf_counter() - t0) * 1e3
+        rounds = [{k: batch_ms(r, cams, W, H, px, a.runs) for k, r in sides.items()} for _ in range(2)]
+        line = {"scene": name, "motion": "large", "angle": angle, "shift": shift, "triangles": len(coords), "width": W,
+                "height": H, "frames": FRAMES, "runs": a.runs, "area_ratio_refit": round(area_ratio, 4),
+                "ref_build_ms": round(ref_build_ms, 2), "upload_ms": round(upload_ms, 2),
+                "build_ms": round(sides["fresh"].scene_info()["build_ms"], 2), "lib_md5": md5}
+        for k in sides:
+            line[f"frame_ms_{k}"] = round(0.5 * (rounds[0][k][0] + rounds[1][k][0]), 4)
+            line[f"frame_ms_{k}_runs"] = [round(rounds[0][k][0], 4), round(rounds[1][k][0], 4)]
+            line[f"frame_ms_{k}_spread"] = [round(min(rounds[0][k][1], rounds[1][k][1]), 4),
+                                            round(max(rounds[0][k][2], rounds[1][k][2]), 4)]
+            line[f"variant_{k}"] = rounds[1][k][3]
+        for mode in ("device", "host"):
+            line[f"rebuild_{mode}"] = info[mode]
+            saved = line["frame_ms_refit"] - line[f"frame_ms_{mode}"]
+            line[f"frames_to_break_even_{mode}"] = round(info[mode]["host_ms"] / saved, 1) if saved > 0 else None
+        emit(json.dumps(line))
+        for r in sides.values():
+            r.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rebuild", action="store_true", help="measure view rebuilds (rt_rebuild_views) instead")
     ap.add_argument("--scenes", nargs="+", default=["dragon", "sportscar", "two_cars", "car_boxed"])
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     a = ap.parse_args()
+
+    def emit(out):
+        print(out, flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(out + "\n")
+
+    if a.rebuild:
+        return rebuild_lines(a, emit)
     import torch
     from prt import device, host
     W, H = a.width, a.height
@@ -127,12 +204,7 @@ def main():
                     "frame_ms_fresh_spread": [round(min(f_fresh[1], f_fresh2[1]), 4), round(max(f_fresh[2], f_fresh2[2]), 4)],
                     "variant_refit": f_refit[3], "variant_fresh": f_fresh[3], "wide_nodes": si["wide_nodes"],
                     "wide_nodes_fresh": fi["wide_nodes"], "lib_md5": md5}
-            out = json.dumps(line)
-            print(out, flush=True)
-            if a.out:
-                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-                with open(a.out, "a") as f:
-                    f.write(out + "\n")
+            emit(json.dumps(line))
             fresh.close()
         r.close()
 
