@@ -363,6 +363,55 @@ typedef struct rt_shade_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info);
 
+/* Multi-hit queries: the k nearest hits and the hit count of the caller's own rays -- what lies behind the first
+ * surface (transmission, thickness, later lidar returns, point-in-mesh parity, closest hits limited to a segment).
+ * For ray i the hit set is
+ *   S_i = { j : hit_triangle(o, d, triangles[j]) = t_j < FLT_MAX and t_j <= t_max[i] }
+ * (hit_triangle: cpu/src/raytracer.c:35-59 with its |det| < EPSILON and t > EPSILON culls), ordered by (t ascending,
+ * original triangle index ascending): a total order, so the answer depends on no BVH. It is what the reference's
+ * brute-force path sees (USE_BVH 0, raytracer.c:115-129), not what bvh_traverse sees: for a direction with a zero
+ * component from an origin on a box face the reference's BVH walk misses geometry that brute force finds (DESIGN.md §2
+ * item 2); here it is found.
+ * tri[i][0..max_hits) and t[i][0..max_hits) receive the first max_hits entries of S_i (unused slots: -1 / FLT_MAX);
+ * count[i] = min(|S_i|, max_hits), or |S_i| itself with count_all (the walk then prunes at t_max only). max_hits = 0
+ * with count_all is a pure counting query. t_max NULL or t_max[i] = +inf: no bound; a NaN or non-positive t_max[i]: the
+ * empty set. No ray value is an error.
+ * RT_KERNEL_STRICT tests every ray against every triangle (the checker: rays x triangles tests, as slow as that
+ * sounds); RT_KERNEL_FAST walks the wide views and answers with the same bits.
+ * A hits query touches nothing a render, a ray query or a shade query owns. */
+#define RT_HITS_MAX 16
+typedef struct rt_hits {
+    const float* origin;   /* device, [n][3] f32 */
+    const float* dir;      /* device, [n][3] f32, NOT normalised by the library */
+    const float* t_max;    /* device, [n] f32, nullable */
+    int n;                 /* >= 0; 0 is RT_OK and launches nothing */
+    int max_hits;          /* 0..RT_HITS_MAX */
+    int count_all;         /* 0 / 1 */
+    int kernel;            /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_hits;
+typedef struct rt_hit_results { /* device pointers: [n][max_hits], [n][max_hits], [n] */
+    int* tri;     /* nullable (with max_hits > 0 not both tri and t) */
+    float* t;     /* nullable */
+    int* count;   /* nullable, except for max_hits = 0 */
+} rt_hit_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null origin / dir with n > 0, max_hits outside 0..RT_HITS_MAX, max_hits > 0 with tri and
+ * t both NULL, max_hits = 0 without count_all and a count pointer, count_all not 0 / 1, an unknown kernel. */
+int rt_trace_hits(rt_ctx* ctx, const rt_hits* rays, const rt_hit_results* out);
+typedef struct rt_hits_info {
+    long long rays, rays_hit;                   /* rays_hit: rays with a non-empty S_i */
+    long long hits_stored, hits_counted;        /* sums of min(|S_i|, max_hits) and of count[i] */
+    long long unit_rays, short_rays, full_rays; /* rays the fast walk served from the unit / primary / full view */
+    long long exhaustive_rays;  /* rays tested against every triangle: all with a valid bound under RT_KERNEL_STRICT,
+                                   those outside the fast walk's domain under RT_KERNEL_FAST (a ray whose t_max makes
+                                   S_i empty walks nothing and is in none of the four) */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_hits_info;
+/* counters of the last hits query (synchronises); RT_E_KERNEL when it overflowed a traversal stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -33,6 +33,7 @@
 #include "rt_feedback.hpp"
 #include "rt_query.hpp"
 #include "rt_shade.hpp"
+#include "rt_hits.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -226,6 +227,11 @@ struct rt_ctx {
     hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
     bool shaded = false, s_launched = false;
     std::unordered_map<const void*, int> s_resident;  // resident workgroups of each k_shade instantiation (0: none fits)
+    // multi-hit queries (rt_trace_hits, rt_hits.hpp): their own again ([rtd::H_NCOUNT] counters, then the chunk counter)
+    unsigned long long* d_hitq = nullptr;
+    hipEvent_t h_ev0 = nullptr, h_ev1 = nullptr;
+    bool hits_traced = false, h_launched = false;
+    std::unordered_map<const void*, int> h_resident;  // resident workgroups of each k_hits instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3074,6 +3080,104 @@ extern "C" int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- multi-hit queries (rt_hits.hpp)
+namespace {
+using HFn = void (*)(rtd::HArgs);
+// the smallest list capacity that holds max_hits (0: the counting build)
+HFn hits_kernel(int max_hits, bool strict) {
+    using rtd::k_hits;
+    if (max_hits == 0) return strict ? k_hits<0, true> : k_hits<0, false>;
+    if (max_hits <= 4) return strict ? k_hits<4, true> : k_hits<4, false>;
+    if (max_hits <= 8) return strict ? k_hits<8, true> : k_hits<8, false>;
+    return strict ? k_hits<16, true> : k_hits<16, false>;
+}
+}  // namespace
+
+extern "C" int rt_trace_hits(rt_ctx* ctx, const rt_hits* r, const rt_hit_results* out) {
+    static_assert(RT_HITS_MAX == rtd::HITS_MAX, "rt_hip.h and rt_hits.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_trace_hits: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_trace_hits: null rays / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_trace_hits: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_trace_hits: negative ray count");
+    if (r->max_hits < 0 || r->max_hits > RT_HITS_MAX) return arg_err(ctx, "rt_trace_hits: max_hits must be 0..16");
+    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_trace_hits: count_all must be 0 or 1");
+    if (r->max_hits == 0 && !r->count_all) return arg_err(ctx, "rt_trace_hits: max_hits = 0 needs count_all");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_trace_hits: null origin / dir");
+    if (r->n > 0 && r->max_hits > 0 && !out->tri && !out->t)
+        return arg_err(ctx, "rt_trace_hits: max_hits > 0 needs a tri or a t output");
+    if (r->n > 0 && r->max_hits == 0 && !out->count)
+        return arg_err(ctx, "rt_trace_hits: a counting query needs a count output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::H_NCOUNT + 1);
+    if (!ctx->d_hitq) HIPC(hipMalloc((void**)&ctx->d_hitq, cbytes));
+    if (!ctx->h_ev0) HIPC(hipEventCreate(&ctx->h_ev0));
+    if (!ctx->h_ev1) HIPC(hipEventCreate(&ctx->h_ev1));
+    HIPC(hipMemsetAsync(ctx->d_hitq, 0, cbytes, ctx->stream));
+    ctx->hits_traced = true;
+    ctx->h_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::HArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the view is chosen per ray)
+    A.origin = r->origin;
+    A.dir = r->dir;
+    A.t_max = r->t_max;
+    A.tri = out->tri;
+    A.t = out->t;
+    A.count = out->count;
+    A.counters = ctx->d_hitq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_hitq + rtd::H_NCOUNT);
+    A.n = r->n;
+    A.o_max = 4.0f * ctx->scene_mx;
+    A.max_hits = r->max_hits;
+    A.count_all = r->count_all;
+    const HFn k = hits_kernel(r->max_hits, r->kernel == RT_KERNEL_STRICT);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->h_resident.find((const void*)k);
+    if (res == ctx->h_resident.end()) res = ctx->h_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->h_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->h_ev1, ctx->stream));
+    ctx->h_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->hits_traced) {
+        ctx->err = "rt_get_hits_info: no hits query traced";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::H_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_hitq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->rays = (long long)c[rtd::H_RAYS];
+    info->rays_hit = (long long)c[rtd::H_RAYS_HIT];
+    info->hits_stored = (long long)c[rtd::H_STORED];
+    info->hits_counted = (long long)c[rtd::H_COUNTED];
+    info->unit_rays = (long long)c[rtd::H_UNIT];
+    info->short_rays = (long long)c[rtd::H_SHORT];
+    info->full_rays = (long long)c[rtd::H_FULL];
+    info->exhaustive_rays = (long long)c[rtd::H_EXH];
+    info->stack_overflows = (long long)c[rtd::H_ERR];
+    if (ctx->h_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->h_ev0, ctx->h_ev1));
+    if (c[rtd::H_ERR]) {
+        ctx->err = "rt_get_hits_info: the query's traversal stack overflowed " + std::to_string(c[rtd::H_ERR]) +
+                   " times (BVH deeper than the walks' stacks): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -3927,6 +4031,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_shq) (void)hipFree(ctx->d_shq);
     if (ctx->s_ev0) (void)hipEventDestroy(ctx->s_ev0);
     if (ctx->s_ev1) (void)hipEventDestroy(ctx->s_ev1);
+    if (ctx->d_hitq) (void)hipFree(ctx->d_hitq);
+    if (ctx->h_ev0) (void)hipEventDestroy(ctx->h_ev0);
+    if (ctx->h_ev1) (void)hipEventDestroy(ctx->h_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

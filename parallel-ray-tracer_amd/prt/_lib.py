@@ -135,6 +135,27 @@ class ShadeInfo(ctypes.Structure):  # rt_shade_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+HITS_MAX = 16  # RT_HITS_MAX
+
+
+class Hits(ctypes.Structure):  # rt_hits
+    _fields_ = [("origin", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("t_max", ctypes.c_void_p),
+                ("n", ctypes.c_int), ("max_hits", ctypes.c_int), ("count_all", ctypes.c_int),
+                ("kernel", ctypes.c_int)]
+
+
+class HitResults(ctypes.Structure):  # rt_hit_results
+    _fields_ = [("tri", ctypes.c_void_p), ("t", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
+class HitsInfo(ctypes.Structure):  # rt_hits_info
+    _fields_ = [("rays", ctypes.c_longlong), ("rays_hit", ctypes.c_longlong), ("hits_stored", ctypes.c_longlong),
+                ("hits_counted", ctypes.c_longlong), ("unit_rays", ctypes.c_longlong),
+                ("short_rays", ctypes.c_longlong), ("full_rays", ctypes.c_longlong),
+                ("exhaustive_rays", ctypes.c_longlong), ("stack_overflows", ctypes.c_longlong),
+                ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -254,6 +275,8 @@ def hip():
         L.rt_get_query_info.argtypes = [ctypes.c_void_p, P(QueryInfo)]
         L.rt_shade_rays.argtypes = [ctypes.c_void_p, P(Shade), P(ShadeResults)]
         L.rt_get_shade_info.argtypes = [ctypes.c_void_p, P(ShadeInfo)]
+        L.rt_trace_hits.argtypes = [ctypes.c_void_p, P(Hits), P(HitResults)]
+        L.rt_get_hits_info.argtypes = [ctypes.c_void_p, P(HitsInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

@@ -439,6 +439,50 @@ class Renderer:
         self._chk(_L.rt_get_shade_info(self._ctx, ctypes.byref(i)), "rt_get_shade_info")
         return {f: getattr(i, f) for f, _ in _lib.ShadeInfo._fields_}
 
+    def trace_hits(self, origins, dirs, max_hits=8, t_max=None, count_all=False, kernel="auto", tri=None, t=None,
+                   count=None):
+        """rt_trace_hits: the max_hits nearest hits of each ray o + t d among ALL triangles hit_triangle accepts with
+        t <= t_max -- ordered by (t, original triangle index), the reference's brute-force answer whatever the BVH ->
+        (tri [n, max_hits] int32, -1 in unused slots; t [n, max_hits] float32, FLT_MAX in unused slots; count [n]
+        int32 = min(hits, max_hits), or every hit of the ray with count_all=True, when the walk prunes at t_max only).
+        max_hits: 0..16; 0 with count_all=True is a pure counting query (tri and t come back empty). t_max: optional
+        [n] float32 tensor (+inf: no bound; NaN or <= 0: no hits). Rays as trace_rays takes them; kernel="strict" tests
+        every triangle (the checker), "fast" / "auto" walks the wide views with the same bits. Asynchronous on the
+        renderer's stream: sync() or hits_info() before the results are read on another stream."""
+        import torch
+        if not isinstance(max_hits, int) or isinstance(max_hits, bool) or not 0 <= max_hits <= _lib.HITS_MAX:
+            raise RtError(f"max_hits: {max_hits!r}, expected an int in 0..{_lib.HITS_MAX}")
+        if max_hits == 0 and not count_all:
+            raise RtError("max_hits = 0 stores nothing: it needs count_all=True")
+        po, pd, n = self._rays(origins, dirs)
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
+            raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
+        pm = _ptr(t_max, "t_max", n, f32, self.device)
+        for x, what, k, dt in ((tri, "tri", n * max_hits, i32), (t, "t", n * max_hits, f32), (count, "count", n, i32)):
+            _ptr(x, what, k, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, max_hits), dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty((n, max_hits), dtype=torch.float32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        res = _lib.HitResults(_ptr(tri, "tri", n * max_hits, i32, self.device) if max_hits else None,
+                              _ptr(t, "t", n * max_hits, f32, self.device) if max_hits else None,
+                              _ptr(count, "count", n, i32, self.device))
+        q = _lib.Hits(po, pd, pm, n, max_hits, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_trace_hits(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_trace_hits")
+        return tri, t, count
+
+    def hits_info(self):
+        """rt_get_hits_info: the last hits query's counters (rays, rays_hit, hits_stored, hits_counted, the rays each
+        view served, exhaustive_rays tested against every triangle) and kernel_ms; synchronises; raises when the query
+        overflowed a stack"""
+        i = _lib.HitsInfo()
+        self._chk(_L.rt_get_hits_info(self._ctx, ctypes.byref(i)), "rt_get_hits_info")
+        return {f: getattr(i, f) for f, _ in _lib.HitsInfo._fields_}
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

@@ -11,9 +11,11 @@ query's counters and the library's md5. Ray sets, each W x H rays:
   window_occluded / window_occluded_perm       the same with every direction inside that window (in_window)
 and, for context beside primary_rows, the frame kernel's own rate (stats()["rays"] / kernel_ms of a `persist` frame).
 The fast and the strict kernel answer with the same bits (checked here on every set).
---mode shade times rt_shade_rays instead (shade_mode below).
+--mode shade times rt_shade_rays instead (shade_mode below), --mode hits rt_trace_hits beside the
+closest-hit query (hits_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
-       python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]"""
+       python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
+       python tools/query_bench.py --mode hits [--runs 7]"""
 import argparse
 import json
 import os
@@ -30,8 +32,9 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade"], default="trace",
-                    help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode)")
+    ap.add_argument("--mode", choices=["trace", "shade", "hits"], default="trace",
+                    help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
+                         "hits: rt_trace_hits beside the closest-hit query (hits_mode)")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -41,6 +44,8 @@ def main():
     md5 = device.lib_md5()
     if a.mode == "shade":
         return shade_mode(a, md5)
+    if a.mode == "hits":
+        return hits_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -176,6 +181,111 @@ def shade_mode(a, md5):
                               "info": {x: v for x, v in last[k].items() if x != "kernel_ms"}, "lib_md5": md5}),
                   flush=True)
         r.close()
+
+
+def hits_mode(a, md5):
+    """--mode hits: per scene, rt_trace_hits on the W x H camera's primary rays in row-major order
+    (primary_rows) and in a fixed random permutation (primary_perm) and on unit-length rays from the primary hit points
+    in random directions (bounce), with max_hits 1, 4, 8, 16 and as a pure count (max_hits 0, count_all), beside the
+    unchanged closest-hit query (rt_trace_rays, fast kernel) on the same rays in the same session (and, for context, that
+    query on a context with RT_FLAG_UNPACKED_TRIS: its build without packed triangle tests). One untimed round
+    first; then --runs rounds with the arms interleaved; kernel_ms from the HIP events around each launch. One JSON line
+    per arm: median / min / max ms, the ratio of the medians to the closest query's, the counters, and two checks: the
+    rays whose first stored t is not the closest query's t (how many, how many of them have a zero direction
+    component, how many the closest query missed altogether, and whether the exhaustive kernel agrees with the fast one
+    on them), and whether the fast kernel equals the exhaustive one on a sample of 2,048 rays (the exhaustive kernel on
+    all of them would be rays x triangles tests)."""
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        # a second context whose closest query runs without packed triangle tests, as rt_trace_hits does: what part of
+        # the distance between the two queries the packed tests are
+        r2 = device.Renderer(0, flags=device.FLAG_UNPACKED_TRIS)
+        r2.upload(s)
+        c = torch.from_numpy(host.camera_array(host.camera(W, H))).cuda()
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device="cuda"),
+                                torch.arange(W, dtype=torch.float32, device="cuda"), indexing="ij")
+        d = ((c[1] - c[0])[None, :] + c[2][None, :] * xs.reshape(-1, 1)) + c[3][None, :] * ys.reshape(-1, 1)
+        o = c[0][None, :].expand_as(d).contiguous()
+        g = torch.Generator(device="cpu").manual_seed(1)
+        perm = torch.randperm(n, generator=g).cuda()
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        t1 = torch.where(hit >= 0, t, torch.ones_like(t))
+        bo = (o + d * t1[:, None]).contiguous()
+        bd = torch.randn(n, 3, generator=g)
+        bd = (bd / bd.norm(dim=1, keepdim=True)).cuda().contiguous()
+        sets = [("primary_rows", o, d), ("primary_perm", o[perm].contiguous(), d[perm].contiguous()), ("bounce", bo, bd)]
+        for label, so, sd in sets:
+            sample = torch.randperm(n, generator=g)[:2048].cuda()
+            po, pd = so[sample].contiguous(), sd[sample].contiguous()
+
+            def closest():
+                out = r.trace_rays(so, sd, kernel="fast")
+                return r.query_info(), out[1]
+
+            def hits(K, count_all=False):
+                out = r.trace_hits(so, sd, max_hits=K, count_all=count_all, kernel="fast")
+                return r.hits_info(), (out[1][:, 0].contiguous() if K else None)
+
+            def sample_equal(K, count_all):
+                x = r.trace_hits(po, pd, max_hits=K, count_all=count_all, kernel="fast")
+                r.sync()
+                y = r.trace_hits(po, pd, max_hits=K, count_all=count_all, kernel="strict")
+                r.sync()
+                return all(bool((p.view(torch.int32) == q.view(torch.int32)).all()) for p, q in zip(x, y))
+
+            def closest_unpacked():  # context: the closest query's build without packed triangle tests
+                out = r2.trace_rays(so, sd, kernel="fast")
+                return r2.query_info(), out[1]
+
+            arms = [("closest", closest)] + [(f"hits{K}", (lambda K=K: hits(K))) for K in (1, 4, 8, 16)]
+            arms.append(("count_all", lambda: hits(0, True)))
+            arms.append(("closest_unpacked_tris", closest_unpacked))
+            checks = {"closest": None, "closest_unpacked_tris": None, "count_all": sample_equal(0, True)}
+            for K in (1, 4, 8, 16):
+                checks[f"hits{K}"] = sample_equal(K, False)
+            _, tc = closest()
+            r.sync()
+            first = {}
+            for k, fn in arms:  # the untimed round, and the first-hit check
+                _, t0 = fn()
+                r.sync()
+                if t0 is None or k.startswith("closest"):
+                    first[k] = None
+                    continue
+                # rays whose first stored t is not the closest query's: bvh_traverse loses hits that brute force finds
+                # (DESIGN.md §3o); how many have a zero direction component, and the exhaustive kernel's word on them
+                idx = torch.nonzero(t0.view(torch.int32) != tc.view(torch.int32)).reshape(-1)
+                first[k] = {"rays": int(idx.numel()), "zero_component": int((sd[idx] == 0).any(1).sum()),
+                            "closest_missed": int((tc[idx] == 3.4028234663852886e38).sum())}
+                if idx.numel():
+                    xo, xd = so[idx].contiguous(), sd[idx].contiguous()
+                    torch.cuda.synchronize()
+                    te = r.trace_hits(xo, xd, max_hits=1, kernel="strict")[1]
+                    r.sync()
+                    first[k]["exhaustive_agrees"] = bool((te[:, 0].view(torch.int32) == t0[idx].view(torch.int32)).all())
+            ms, last = {k: [] for k, _ in arms}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _ = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            base = statistics.median(ms["closest"])
+            for k, _ in arms:
+                med = statistics.median(ms[k])
+                print(json.dumps({"scene": name, "set": label, "arm": k, "rays": n, "width": W, "height": H,
+                                  "mrays_s": round(n / med / 1e3, 1), "kernel_ms_median": round(med, 4),
+                                  "kernel_ms_min": round(min(ms[k]), 4), "kernel_ms_max": round(max(ms[k]), 4),
+                                  "ratio_to_closest": round(med / base, 3), "runs": a.runs,
+                                  "first_t_differs_from_closest": first[k], "sample_equals_exhaustive": checks[k],
+                                  "info": {x: v for x, v in last[k].items() if x != "kernel_ms"}, "lib_md5": md5}),
+                      flush=True)
+        r.close()
+        r2.close()
 
 
 def in_window(d):
