@@ -412,6 +412,71 @@ typedef struct rt_hits_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info);
 
+/* Nearest-surface queries: per caller-supplied point the nearest triangle, the closest point on it and the squared
+ * distance (distance fields, clearance tests, snapping samples to a surface, closest-point correspondences).
+ * Query i is a point q with an optional bound max_dist2[i]. Its candidate set is
+ *   S_i = { j : D(q, triangle j) <= min(max_dist2[i], FLT_MAX) }, ordered by (D ascending, original index ascending),
+ * and the answer is its first element: a total order, so the answer depends on no BVH, and triangles that share the
+ * nearest vertex or edge (an exact tie, common on ordinary meshes) answer with the lowest index.
+ * D and the closest point P are defined on a triangle's record a = v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0) by Ericson's
+ * region algorithm (Real-Time Collision Detection 5.1.5), every operation one float32 operation, dot(u, v) evaluated as
+ * u.x*v.x + u.y*v.y + u.z*v.z left to right, nothing contracted into an FMA:
+ *   ap = q - a;   d1 = dot(e1, ap);  d2 = dot(e2, ap)
+ *   bp = ap - e1; d3 = dot(e1, bp);  d4 = dot(e2, bp)
+ *   cp = ap - e2; d5 = dot(e1, cp);  d6 = dot(e2, cp)
+ *   vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *   the first condition that holds, in this order:
+ *     d1 <= 0 && d2 <= 0                   p = a
+ *     d3 >= 0 && d4 <= d3                  p = a + e1
+ *     vc <= 0 && d1 >= 0 && d3 <= 0        p = a + e1 * (d1 / (d1 - d3))
+ *     d6 >= 0 && d5 <= d6                  p = a + e2
+ *     vb <= 0 && d2 >= 0 && d6 <= 0        p = a + e2 * (d2 / (d2 - d6))
+ *     va <= 0 && x >= 0 && y >= 0          p = (a + e1) + (e2 - e1) * (x / (x + y)),  x = d4 - d3, y = d5 - d6
+ *     otherwise  den = 1 / ((va + vb) + vc); p = (a + e1 * (vb * den)) + e2 * (vc * den)
+ *   lo = fminf(fminf(a, a + e1), a + e2); hi = fmaxf(fmaxf(a, a + e1), a + e2)     per component
+ *   P = fminf(fmaxf(p, lo), hi)                                  per component, C semantics: a NaN operand loses
+ *   df = q - P;  D = dot(df, df)
+ * The clamp into the triangle's own box is part of the definition: P is finite for every finite triangle (a degenerate
+ * triangle's 0 / 0 becomes a corner of its box -- such a P need not lie on the triangle), and the walk prunes with no
+ * tuned margin. P at the second or third vertex is fl(a + e1) or fl(a + e2): the vertex itself or a
+ * neighbouring float.
+ * Results: tri[i] = the original triangle index, d2[i] = D, point[i] = P. The empty set gives -1, FLT_MAX and q's own
+ * bits; it is empty when nothing lies within the bound, when max_dist2[i] is NaN or negative (0 is a valid bound: points
+ * on the surface), and for a non-finite q (decided before any walk). max_dist2 NULL or +inf: no bound. A finite q so
+ * far away that D overflows has the empty set. No input value is an error.
+ * RT_KERNEL_STRICT tests every point against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * boxes ordered and pruned by their distance to the point, and answers with the same bits; a scene without a wide view
+ * (RT_ACCEL_REFERENCE) runs the exhaustive loop under either kernel.
+ * A nearest query touches nothing a render, a ray query, a shade query or a hits query owns. */
+typedef struct rt_points {
+    const float* point;     /* device, [n][3] f32 */
+    const float* max_dist2; /* device, [n] f32, nullable */
+    int n;                  /* >= 0; 0 is RT_OK and launches nothing */
+    int kernel;             /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_points;
+typedef struct rt_nearest_results { /* device pointers, all nullable, at least one non-null when n > 0 */
+    int* tri;     /* [n] */
+    float* d2;    /* [n] */
+    float* point; /* [n][3] */
+} rt_nearest_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, a null point with n > 0, all three outputs NULL with n > 0, an unknown kernel. */
+int rt_nearest_points(rt_ctx* ctx, const rt_points* points, const rt_nearest_results* out);
+typedef struct rt_nearest_info {
+    long long points, found;      /* found: points with a non-empty S_i */
+    long long walked_points;      /* points that walked the wide view */
+    long long exhaustive_points;  /* points tested against every triangle: all valid ones under RT_KERNEL_STRICT or
+                                     without a wide view (a non-finite point or a NaN / negative bound is in neither) */
+    long long empty_points;       /* points - found */
+    long long nodes_visited;      /* wide nodes decoded, summed over the points (a level popped again counts again) */
+    long long tris_tested;        /* triangle tests, summed over the points (exhaustive: points x triangles) */
+    long long stack_overflows;    /* must be 0 */
+    float kernel_ms;              /* HIP events around the query's launch */
+} rt_nearest_info;
+/* counters of the last nearest query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -34,6 +34,7 @@
 #include "rt_query.hpp"
 #include "rt_shade.hpp"
 #include "rt_hits.hpp"
+#include "rt_nearest.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -232,6 +233,12 @@ struct rt_ctx {
     hipEvent_t h_ev0 = nullptr, h_ev1 = nullptr;
     bool hits_traced = false, h_launched = false;
     std::unordered_map<const void*, int> h_resident;  // resident workgroups of each k_hits instantiation
+    // nearest-surface queries (rt_nearest_points, rt_nearest.hpp): their own again ([rtd::N_NCOUNT] counters, then the
+    // chunk counter)
+    unsigned long long* d_nearq = nullptr;
+    hipEvent_t n_ev0 = nullptr, n_ev1 = nullptr;
+    bool nearest_run = false, n_launched = false;
+    std::unordered_map<const void*, int> n_resident;  // resident workgroups of each k_nearest instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3178,6 +3185,81 @@ extern "C" int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- nearest-surface queries (rt_nearest.hpp)
+extern "C" int rt_nearest_points(rt_ctx* ctx, const rt_points* r, const rt_nearest_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_nearest_points: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_nearest_points: null points / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_nearest_points: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_nearest_points: negative point count");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && !r->point) return arg_err(ctx, "rt_nearest_points: null point");
+    if (r->n > 0 && !out->tri && !out->d2 && !out->point)
+        return arg_err(ctx, "rt_nearest_points: needs a tri, a d2 or a point output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::N_NCOUNT + 1);
+    if (!ctx->d_nearq) HIPC(hipMalloc((void**)&ctx->d_nearq, cbytes));
+    if (!ctx->n_ev0) HIPC(hipEventCreate(&ctx->n_ev0));
+    if (!ctx->n_ev1) HIPC(hipEventCreate(&ctx->n_ev1));
+    HIPC(hipMemsetAsync(ctx->d_nearq, 0, cbytes, ctx->stream));
+    ctx->nearest_run = true;
+    ctx->n_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::NArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.point = r->point;
+    A.max_dist2 = r->max_dist2;
+    A.tri = out->tri;
+    A.d2 = out->d2;
+    A.out = out->point;
+    A.counters = ctx->d_nearq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_nearq + rtd::N_NCOUNT);
+    A.n = r->n;
+    void (*k)(rtd::NArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_nearest<true> : rtd::k_nearest<false>;
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->n_resident.find((const void*)k);
+    if (res == ctx->n_resident.end()) res = ctx->n_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->n_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->n_ev1, ctx->stream));
+    ctx->n_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->nearest_run) {
+        ctx->err = "rt_get_nearest_info: no nearest query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::N_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_nearq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->points = (long long)c[rtd::N_POINTS];
+    info->found = (long long)c[rtd::N_FOUND];
+    info->walked_points = (long long)c[rtd::N_WALKED];
+    info->exhaustive_points = (long long)c[rtd::N_EXH];
+    info->empty_points = (long long)c[rtd::N_EMPTY];
+    info->nodes_visited = (long long)c[rtd::N_NODES];
+    info->tris_tested = (long long)c[rtd::N_TRIS];
+    info->stack_overflows = (long long)c[rtd::N_ERR];
+    if (ctx->n_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->n_ev0, ctx->n_ev1));
+    if (c[rtd::N_ERR]) {
+        ctx->err = "rt_get_nearest_info: the query's traversal stack overflowed " + std::to_string(c[rtd::N_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4034,6 +4116,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_hitq) (void)hipFree(ctx->d_hitq);
     if (ctx->h_ev0) (void)hipEventDestroy(ctx->h_ev0);
     if (ctx->h_ev1) (void)hipEventDestroy(ctx->h_ev1);
+    if (ctx->d_nearq) (void)hipFree(ctx->d_nearq);
+    if (ctx->n_ev0) (void)hipEventDestroy(ctx->n_ev0);
+    if (ctx->n_ev1) (void)hipEventDestroy(ctx->n_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

@@ -156,6 +156,22 @@ class HitsInfo(ctypes.Structure):  # rt_hits_info
                 ("kernel_ms", ctypes.c_float)]
 
 
+class Points(ctypes.Structure):  # rt_points
+    _fields_ = [("point", ctypes.c_void_p), ("max_dist2", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("kernel", ctypes.c_int)]
+
+
+class NearestResults(ctypes.Structure):  # rt_nearest_results
+    _fields_ = [("tri", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("point", ctypes.c_void_p)]
+
+
+class NearestInfo(ctypes.Structure):  # rt_nearest_info
+    _fields_ = [("points", ctypes.c_longlong), ("found", ctypes.c_longlong), ("walked_points", ctypes.c_longlong),
+                ("exhaustive_points", ctypes.c_longlong), ("empty_points", ctypes.c_longlong),
+                ("nodes_visited", ctypes.c_longlong), ("tris_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -277,6 +293,8 @@ def hip():
         L.rt_get_shade_info.argtypes = [ctypes.c_void_p, P(ShadeInfo)]
         L.rt_trace_hits.argtypes = [ctypes.c_void_p, P(Hits), P(HitResults)]
         L.rt_get_hits_info.argtypes = [ctypes.c_void_p, P(HitsInfo)]
+        L.rt_nearest_points.argtypes = [ctypes.c_void_p, P(Points), P(NearestResults)]
+        L.rt_get_nearest_info.argtypes = [ctypes.c_void_p, P(NearestInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

@@ -483,6 +483,60 @@ class Renderer:
         self._chk(_L.rt_get_hits_info(self._ctx, ctypes.byref(i)), "rt_get_hits_info")
         return {f: getattr(i, f) for f, _ in _lib.HitsInfo._fields_}
 
+    def nearest(self, points, max_dist2=None, kernel="auto", tri=None, d2=None, point=None):
+        """rt_nearest_points: per point the nearest triangle of the scene, the squared distance to it and the closest
+        point on it -- the first triangle by (D, original triangle index), whatever the BVH (include/rt_hip.h states D
+        and P) -> (tri [n] int32, -1 when nothing lies within the bound; d2 [n] float32, FLT_MAX then; point [n, 3]
+        float32, the query point's own bits then). points: a [n, 3] float32 contiguous tensor on this device, or a raw
+        (pointer, n).
+        max_dist2: optional [n] float32 tensor of squared bounds (+inf: none; 0: points on the surface; NaN or
+        negative: nothing). kernel="strict" tests every triangle (the checker), "fast" / "auto" walks the full wide view
+        with the same bits. tri / d2 / point: optional outputs (allocated when not given). Asynchronous on the
+        renderer's stream: sync() or nearest_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if isinstance(points, tuple):  # a raw pointer: (pointer, n)
+            pp, n = points
+            if not isinstance(pp, int) or not isinstance(n, int) or n < 0:
+                raise RtError("points: a raw pointer is given as points=(pointer, n)")
+        else:
+            if not isinstance(points, torch.Tensor):
+                raise RtError(f"points: expected a torch tensor or a raw (pointer, n), got {type(points).__name__}")
+            if points.dim() != 2 or points.shape[1] != 3:
+                raise RtError(f"points: shape {tuple(points.shape)}, expected [n, 3]")
+            n = points.shape[0]
+        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
+            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
+        if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
+        if not isinstance(points, tuple):
+            pp = _ptr(points, "points", 3 * n, f32, self.device)
+        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
+            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
+        pm = _ptr(max_dist2, "max_dist2", n, f32, self.device)
+        for x, what, k, dt in ((tri, "tri", n, i32), (d2, "d2", n, f32), (point, "point", 3 * n, f32)):
+            _ptr(x, what, k, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        if d2 is None:
+            d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        if point is None:
+            point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        res = _lib.NearestResults(_ptr(tri, "tri", n, i32, self.device), _ptr(d2, "d2", n, f32, self.device),
+                                  _ptr(point, "point", 3 * n, f32, self.device))
+        q = _lib.Points(pp, pm, n, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_nearest_points(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_nearest_points")
+        return tri, d2, point
+
+    def nearest_info(self):
+        """rt_get_nearest_info: the last nearest query's counters (points, found, walked_points, exhaustive_points,
+        empty_points, nodes_visited, tris_tested) and kernel_ms; synchronises; raises when the query overflowed its
+        stack"""
+        i = _lib.NearestInfo()
+        self._chk(_L.rt_get_nearest_info(self._ctx, ctypes.byref(i)), "rt_get_nearest_info")
+        return {f: getattr(i, f) for f, _ in _lib.NearestInfo._fields_}
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

@@ -12,10 +12,11 @@ query's counters and the library's md5. Ray sets, each W x H rays:
 and, for context beside primary_rows, the frame kernel's own rate (stats()["rays"] / kernel_ms of a `persist` frame).
 The fast and the strict kernel answer with the same bits (checked here on every set).
 --mode shade times rt_shade_rays instead (shade_mode below), --mode hits rt_trace_hits beside the
-closest-hit query (hits_mode below).
+closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
-       python tools/query_bench.py --mode hits [--runs 7]"""
+       python tools/query_bench.py --mode hits [--runs 7]
+       python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -32,9 +33,11 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits"], default="trace",
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest"], default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
-                         "hits: rt_trace_hits beside the closest-hit query (hits_mode)")
+                         "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
+                         "nearest: rt_nearest_points beside the closest-hit query (nearest_mode)")
+    ap.add_argument("--out", default=None, help="nearest: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -46,6 +49,8 @@ def main():
         return shade_mode(a, md5)
     if a.mode == "hits":
         return hits_mode(a, md5)
+    if a.mode == "nearest":
+        return nearest_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -286,6 +291,91 @@ def hits_mode(a, md5):
                       flush=True)
         r.close()
         r2.close()
+
+
+def nearest_mode(a, md5):
+    """--mode nearest: per scene, rt_nearest_points on three sets of W x H points -- the camera's
+    primary hit points pushed 0.05 along the ray (near the surface, coherent; a missing ray's point lies at t = 1), the
+    same points in a fixed random permutation, and uniform points in the scene's box grown by a quarter -- with the fast
+    kernel, beside the closest-hit query (rt_trace_rays, fast kernel) on the same count of camera rays for scale and the
+    exhaustive kernel on 4,096 of the points. One untimed round first; then --runs rounds with the arms interleaved;
+    kernel_ms from the HIP events around each launch. One JSON line per arm: median / min / max ms, the ratios of the
+    medians to the closest query's and (per point) to the exhaustive kernel's, nodes_visited and tris_tested per point,
+    the counters, and whether the fast kernel equals the exhaustive one on the 4,096 points."""
+    import numpy as np
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        c = torch.from_numpy(host.camera_array(host.camera(W, H))).cuda()
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device="cuda"),
+                                torch.arange(W, dtype=torch.float32, device="cuda"), indexing="ij")
+        d = ((c[1] - c[0])[None, :] + c[2][None, :] * xs.reshape(-1, 1)) + c[3][None, :] * ys.reshape(-1, 1)
+        o = c[0][None, :].expand_as(d).contiguous()
+        g = torch.Generator(device="cpu").manual_seed(1)
+        perm = torch.randperm(n, generator=g).cuda()
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        t1 = torch.where(hit >= 0, t, torch.ones_like(t))
+        near = (o + d * (t1 + 0.05)[:, None]).contiguous()
+        co = torch.from_numpy(np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3))
+        lo, hi = co.min(0).values, co.max(0).values
+        grow = (hi - lo) / 4
+        uni = (torch.rand(n, 3, generator=g) * (hi - lo + 2 * grow) + (lo - grow)).cuda().contiguous()
+        sets = [("near_surface", near), ("near_surface_perm", near[perm].contiguous()), ("uniform_box", uni)]
+        for label, pts in sets:
+            sample = pts[torch.randperm(n, generator=g)[:NS].cuda()].contiguous()
+
+            def closest():
+                r.trace_rays(o, d, kernel="fast")
+                return r.query_info(), n
+
+            def fast():
+                r.nearest(pts, kernel="fast")
+                return r.nearest_info(), n
+
+            def exhaustive():
+                r.nearest(sample, kernel="strict")
+                return r.nearest_info(), NS
+
+            x = r.nearest(sample, kernel="fast")
+            r.sync()
+            y = r.nearest(sample, kernel="strict")
+            r.sync()
+            same = all(bool((p.view(torch.int32) == q.view(torch.int32)).all()) for p, q in zip(x, y))
+            arms = [("nearest_fast", fast), ("closest", closest), ("nearest_exhaustive_4096", exhaustive)]
+            for _, fn in arms:  # the untimed round
+                fn()
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                line = {"scene": name, "set": label, "arm": k, "points": cnt[k], "width": W, "height": H,
+                        "mpoints_s": round(cnt[k] / med[k] / 1e3, 2), "kernel_ms_median": round(med[k], 4),
+                        "kernel_ms_min": round(min(ms[k]), 4), "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_closest": round(med[k] / med["closest"], 3),
+                        "per_point_ratio_to_exhaustive": round((med[k] / cnt[k]) / (med["nearest_exhaustive_4096"] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same if k == "nearest_fast" else None,
+                        "info": {x: v for x, v in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                if "nodes_visited" in info:
+                    line["nodes_visited_per_point"] = round(info["nodes_visited"] / cnt[k], 2)
+                    line["tris_tested_per_point"] = round(info["tris_tested"] / cnt[k], 2)
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+        r.close()
+    if out:
+        out.close()
 
 
 def in_window(d):
