@@ -477,6 +477,62 @@ typedef struct rt_nearest_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info);
 
+/* Neighbour queries: per caller-supplied point the k nearest triangles and the number of triangles within a radius --
+ * rt_nearest_points' plural form (contacts of a particle against every triangle within its radius, several candidates
+ * of a correspondence search, blending over the nearest few faces, density and clearance estimates, and the whole fan
+ * of triangles that tie exactly at a shared vertex, of which rt_nearest_points answers one).
+ * Query i is a point q with an optional bound max_dist2[i]. Its candidate set is rt_nearest_points' own, in its order:
+ *   S_i = { j : D(q, triangle j) <= min(max_dist2[i], FLT_MAX) }, ordered by (D ascending, original index ascending),
+ * D and P exactly as the block above states them.
+ * tri[i][0..max_tris) receives the first max_tris entries of S_i (unused slots: -1), d2[i][0..max_tris) their D (unused
+ * slots: FLT_MAX), point[i][0..max_tris)[3] their P (unused slots: q's own bits). count[i] = min(|S_i|, max_tris), or
+ * |S_i| itself with count_all; max_tris = 0 with count_all is a pure radius count.
+ * S_i is empty when nothing lies within the bound, when max_dist2[i] is NaN or negative (0 is a valid bound) and for a
+ * non-finite q (decided before any walk). max_dist2 NULL or +inf: no bound; with count_all the query then counts every
+ * triangle whose D does not overflow, which costs a full traversal of the scene. No input value is an error.
+ * With max_tris = 1 and no count_all, tri, d2 and point are rt_nearest_points' answer bit for bit.
+ * RT_KERNEL_STRICT tests every point against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * pruning at min(the bound, the max_tris-th D found so far) -- at the bound alone with count_all -- and answers with
+ * the same bits; a scene without a wide view (RT_ACCEL_REFERENCE) runs the exhaustive loop under
+ * either kernel.
+ * A neighbours query touches nothing a render or any other query owns. */
+#define RT_NEIGHBOURS_MAX 16
+typedef struct rt_neighbours {
+    const float* point;     /* device, [n][3] f32 */
+    const float* max_dist2; /* device, [n] f32, nullable */
+    int n;                  /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;           /* 0..RT_NEIGHBOURS_MAX */
+    int count_all;          /* 0 / 1 */
+    int kernel;             /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_neighbours;
+typedef struct rt_neighbour_results { /* device pointers, all nullable: [n][max_tris], [n][max_tris],
+                                         [n][max_tris][3], [n] */
+    int* tri;
+    float* d2;
+    float* point;
+    int* count;   /* required for max_tris = 0 */
+} rt_neighbour_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, a null point with n > 0, max_tris outside 0..RT_NEIGHBOURS_MAX, max_tris > 0 with tri, d2
+ * and point all NULL, max_tris = 0 without count_all and a count pointer, count_all not 0 / 1, an unknown kernel, a
+ * negative n. */
+int rt_nearest_tris(rt_ctx* ctx, const rt_neighbours* points, const rt_neighbour_results* out);
+typedef struct rt_neighbours_info {
+    long long points, found;              /* found: points with a non-empty S_i */
+    long long tris_stored, tris_counted;  /* sums of min(|S_i|, max_tris) and of count[i] */
+    long long walked_points;              /* points that walked the wide view */
+    long long exhaustive_points;  /* points tested against every triangle: all valid ones under RT_KERNEL_STRICT or
+                                     without a wide view (a non-finite point or a NaN / negative bound is in neither) */
+    long long empty_points;       /* points - found */
+    long long nodes_visited;      /* wide nodes decoded, summed over the points (a level popped again counts again) */
+    long long tris_tested;        /* triangle tests, summed over the points (exhaustive: points x triangles) */
+    long long stack_overflows;    /* must be 0 */
+    float kernel_ms;              /* HIP events around the query's launch */
+} rt_neighbours_info;
+/* counters of the last neighbours query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results
+ * are not valid), RT_E_STATE before the first */
+int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -35,6 +35,7 @@
 #include "rt_shade.hpp"
 #include "rt_hits.hpp"
 #include "rt_nearest.hpp"
+#include "rt_neighbours.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -239,6 +240,14 @@ struct rt_ctx {
     hipEvent_t n_ev0 = nullptr, n_ev1 = nullptr;
     bool nearest_run = false, n_launched = false;
     std::unordered_map<const void*, int> n_resident;  // resident workgroups of each k_nearest instantiation
+    // neighbour queries (rt_nearest_tris, rt_neighbours.hpp): their own again ([rtd::B_NCOUNT] counters, then the chunk
+    // counter); d_ref_inv: original triangle index -> position in the reference tree's records, made by the first
+    // query of a scene that asks for points (freed with the scene)
+    unsigned long long* d_nbq = nullptr;
+    hipEvent_t b_ev0 = nullptr, b_ev1 = nullptr;
+    bool neighbours_run = false, b_launched = false;
+    std::unordered_map<const void*, int> b_resident;  // resident workgroups of each k_neighbours instantiation
+    int* d_ref_inv = nullptr;
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -369,6 +378,8 @@ void free_scene(rt_ctx* ctx) {
     }
     free_view(ctx->ref);
     free_view(ctx->acc);
+    if (ctx->d_ref_inv) (void)hipFree(ctx->d_ref_inv);
+    ctx->d_ref_inv = nullptr;
     for (DevWide* w : {&ctx->wide, &ctx->unit, &ctx->prim}) free_wide(*w);
     for (void* p : {(void*)ctx->d_shade, (void*)ctx->d_mats, (void*)ctx->d_lights, (void*)ctx->d_faces})
         if (p) (void)hipFree(p);
@@ -3260,6 +3271,115 @@ extern "C" int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- neighbour queries (rt_neighbours.hpp)
+namespace {
+using BFn = void (*)(rtd::BArgs);
+// the smallest list capacity that holds max_tris (0: the counting build)
+BFn neighbours_kernel(int max_tris, bool strict) {
+    using rtd::k_neighbours;
+    if (max_tris == 0) return strict ? k_neighbours<0, true> : k_neighbours<0, false>;
+    if (max_tris <= 4) return strict ? k_neighbours<4, true> : k_neighbours<4, false>;
+    if (max_tris <= 8) return strict ? k_neighbours<8, true> : k_neighbours<8, false>;
+    return strict ? k_neighbours<16, true> : k_neighbours<16, false>;
+}
+}  // namespace
+
+extern "C" int rt_nearest_tris(rt_ctx* ctx, const rt_neighbours* r, const rt_neighbour_results* out) {
+    static_assert(RT_NEIGHBOURS_MAX == rtd::NEIGHBOURS_MAX, "rt_hip.h and rt_neighbours.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_nearest_tris: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_nearest_tris: null points / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_nearest_tris: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_nearest_tris: negative point count");
+    if (r->max_tris < 0 || r->max_tris > RT_NEIGHBOURS_MAX) return arg_err(ctx, "rt_nearest_tris: max_tris must be 0..16");
+    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_nearest_tris: count_all must be 0 or 1");
+    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_nearest_tris: max_tris = 0 needs count_all");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && !r->point) return arg_err(ctx, "rt_nearest_tris: null point");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->d2 && !out->point)
+        return arg_err(ctx, "rt_nearest_tris: max_tris > 0 needs a tri, a d2 or a point output");
+    if (r->n > 0 && r->max_tris == 0 && !out->count)
+        return arg_err(ctx, "rt_nearest_tris: a counting query needs a count output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::B_NCOUNT + 1);
+    if (!ctx->d_nbq) HIPC(hipMalloc((void**)&ctx->d_nbq, cbytes));
+    if (!ctx->b_ev0) HIPC(hipEventCreate(&ctx->b_ev0));
+    if (!ctx->b_ev1) HIPC(hipEventCreate(&ctx->b_ev1));
+    HIPC(hipMemsetAsync(ctx->d_nbq, 0, cbytes, ctx->stream));
+    ctx->neighbours_run = true;
+    ctx->b_launched = false;
+    if (r->n == 0) return RT_OK;
+    const bool want_p = r->max_tris > 0 && out->point;
+    if (want_p && !ctx->d_ref_inv) {  // original index -> the reference tree's record (rt_neighbours.hpp ref_inv)
+        const int nt = ctx->n_tris;
+        HIPC(hipMalloc((void**)&ctx->d_ref_inv, sizeof(int) * (size_t)std::max(nt, 1)));
+        HIPC(hipMemsetAsync(ctx->d_ref_inv, 0, sizeof(int) * (size_t)std::max(nt, 1), ctx->stream));
+        if (nt > 0) {
+            rtd::k_invert_orig<<<(nt + 255) / 256, 256, 0, ctx->stream>>>(ctx->ref.orig, nt, ctx->d_ref_inv);
+            HIPC(hipGetLastError());
+        }
+    }
+    rtd::BArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.point = r->point;
+    A.max_dist2 = r->max_dist2;
+    A.tri = r->max_tris > 0 ? out->tri : nullptr;
+    A.d2 = r->max_tris > 0 ? out->d2 : nullptr;
+    A.out = want_p ? out->point : nullptr;
+    A.count = out->count;
+    A.ref_inv = ctx->d_ref_inv;
+    A.counters = ctx->d_nbq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_nbq + rtd::B_NCOUNT);
+    A.n = r->n;
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    const BFn k = neighbours_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->b_resident.find((const void*)k);
+    if (res == ctx->b_resident.end()) res = ctx->b_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->b_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->b_ev1, ctx->stream));
+    ctx->b_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->neighbours_run) {
+        ctx->err = "rt_get_neighbours_info: no neighbours query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::B_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_nbq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->points = (long long)c[rtd::B_POINTS];
+    info->found = (long long)c[rtd::B_FOUND];
+    info->tris_stored = (long long)c[rtd::B_STORED];
+    info->tris_counted = (long long)c[rtd::B_COUNTED];
+    info->walked_points = (long long)c[rtd::B_WALKED];
+    info->exhaustive_points = (long long)c[rtd::B_EXH];
+    info->empty_points = (long long)c[rtd::B_EMPTY];
+    info->nodes_visited = (long long)c[rtd::B_NODES];
+    info->tris_tested = (long long)c[rtd::B_TRIS];
+    info->stack_overflows = (long long)c[rtd::B_ERR];
+    if (ctx->b_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->b_ev0, ctx->b_ev1));
+    if (c[rtd::B_ERR]) {
+        ctx->err = "rt_get_neighbours_info: the query's traversal stack overflowed " + std::to_string(c[rtd::B_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4119,6 +4239,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_nearq) (void)hipFree(ctx->d_nearq);
     if (ctx->n_ev0) (void)hipEventDestroy(ctx->n_ev0);
     if (ctx->n_ev1) (void)hipEventDestroy(ctx->n_ev1);
+    if (ctx->d_nbq) (void)hipFree(ctx->d_nbq);
+    if (ctx->b_ev0) (void)hipEventDestroy(ctx->b_ev0);
+    if (ctx->b_ev1) (void)hipEventDestroy(ctx->b_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

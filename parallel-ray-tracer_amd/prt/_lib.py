@@ -172,6 +172,27 @@ class NearestInfo(ctypes.Structure):  # rt_nearest_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+NEIGHBOURS_MAX = 16  # RT_NEIGHBOURS_MAX
+
+
+class Neighbours(ctypes.Structure):  # rt_neighbours
+    _fields_ = [("point", ctypes.c_void_p), ("max_dist2", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("max_tris", ctypes.c_int), ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class NeighbourResults(ctypes.Structure):  # rt_neighbour_results
+    _fields_ = [("tri", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("point", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
+class NeighboursInfo(ctypes.Structure):  # rt_neighbours_info
+    _fields_ = [("points", ctypes.c_longlong), ("found", ctypes.c_longlong), ("tris_stored", ctypes.c_longlong),
+                ("tris_counted", ctypes.c_longlong), ("walked_points", ctypes.c_longlong),
+                ("exhaustive_points", ctypes.c_longlong), ("empty_points", ctypes.c_longlong),
+                ("nodes_visited", ctypes.c_longlong), ("tris_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -295,6 +316,8 @@ def hip():
         L.rt_get_hits_info.argtypes = [ctypes.c_void_p, P(HitsInfo)]
         L.rt_nearest_points.argtypes = [ctypes.c_void_p, P(Points), P(NearestResults)]
         L.rt_get_nearest_info.argtypes = [ctypes.c_void_p, P(NearestInfo)]
+        L.rt_nearest_tris.argtypes = [ctypes.c_void_p, P(Neighbours), P(NeighbourResults)]
+        L.rt_get_neighbours_info.argtypes = [ctypes.c_void_p, P(NeighboursInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

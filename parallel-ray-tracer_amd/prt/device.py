@@ -537,6 +537,71 @@ class Renderer:
         self._chk(_L.rt_get_nearest_info(self._ctx, ctypes.byref(i)), "rt_get_nearest_info")
         return {f: getattr(i, f) for f, _ in _lib.NearestInfo._fields_}
 
+    def nearest_tris(self, points, k=8, max_dist2=None, count_all=False, points_out=False, kernel="auto", tri=None,
+                     d2=None, count=None, point=None):
+        """rt_nearest_tris: per point the k nearest triangles of the scene -- the first k by (D, original triangle
+        index) among those with D <= max_dist2, nearest's own order (include/rt_hip.h) -> (tri [n, k] int32, -1 in
+        unused slots; d2 [n, k] float32, FLT_MAX in unused slots; count [n] int32 = min(triangles within the bound, k),
+        or every triangle within the bound with count_all=True, when the walk prunes at the bound only), plus point
+        [n, k, 3] float32 (the closest point on each triangle; the query point's own bits in unused slots) with
+        points_out=True or a `point` output. k: 0..16; 0 with count_all=True is a pure radius count (tri and d2 come
+        back empty). With k = 1 the answer is nearest's, bit for bit. points, max_dist2 and kernel as nearest takes
+        them; without a bound count_all counts every triangle of the scene, a full traversal. tri / d2 / count / point:
+        optional outputs (allocated when not given). Asynchronous on the renderer's stream: sync() or
+        neighbours_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.NEIGHBOURS_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.NEIGHBOURS_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        if isinstance(points, tuple):  # a raw pointer: (pointer, n)
+            pp, n = points
+            if not isinstance(pp, int) or not isinstance(n, int) or n < 0:
+                raise RtError("points: a raw pointer is given as points=(pointer, n)")
+        else:
+            if not isinstance(points, torch.Tensor):
+                raise RtError(f"points: expected a torch tensor or a raw (pointer, n), got {type(points).__name__}")
+            if points.dim() != 2 or points.shape[1] != 3:
+                raise RtError(f"points: shape {tuple(points.shape)}, expected [n, 3]")
+            n = points.shape[0]
+        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
+            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
+        if isinstance(point, torch.Tensor) and (point.dim() != 3 or tuple(point.shape[1:]) != (k, 3)):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, {k}, 3]")
+        if not isinstance(points, tuple):
+            pp = _ptr(points, "points", 3 * n, f32, self.device)
+        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
+            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
+        pm = _ptr(max_dist2, "max_dist2", n, f32, self.device)
+        for x, what, m, dt in ((tri, "tri", n * k, i32), (d2, "d2", n * k, f32), (count, "count", n, i32),
+                               (point, "point", 3 * n * k, f32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if d2 is None:
+            d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        if point is None and points_out:
+            point = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        res = _lib.NeighbourResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                                    _ptr(d2, "d2", n * k, f32, self.device) if k else None,
+                                    _ptr(point, "point", 3 * n * k, f32, self.device) if k else None,
+                                    _ptr(count, "count", n, i32, self.device))
+        q = _lib.Neighbours(pp, pm, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_nearest_tris(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_nearest_tris")
+        return (tri, d2, count) if point is None else (tri, d2, count, point)
+
+    def neighbours_info(self):
+        """rt_get_neighbours_info: the last neighbours query's counters (points, found, tris_stored, tris_counted,
+        walked_points, exhaustive_points, empty_points, nodes_visited, tris_tested) and kernel_ms; synchronises; raises
+        when the query overflowed its stack"""
+        i = _lib.NeighboursInfo()
+        self._chk(_L.rt_get_neighbours_info(self._ctx, ctypes.byref(i)), "rt_get_neighbours_info")
+        return {f: getattr(i, f) for f, _ in _lib.NeighboursInfo._fields_}
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

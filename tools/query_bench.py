@@ -12,11 +12,13 @@ query's counters and the library's md5. Ray sets, each W x H rays:
 and, for context beside primary_rows, the frame kernel's own rate (stats()["rays"] / kernel_ms of a `persist` frame).
 The fast and the strict kernel answer with the same bits (checked here on every set).
 --mode shade times rt_shade_rays instead (shade_mode below), --mode hits rt_trace_hits beside the
-closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below).
+closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below),
+--mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
-       python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -33,11 +35,12 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest"], default="trace",
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours"], default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
-                         "nearest: rt_nearest_points beside the closest-hit query (nearest_mode)")
-    ap.add_argument("--out", default=None, help="nearest: also append the raw lines to this file")
+                         "nearest: rt_nearest_points beside the closest-hit query (nearest_mode); "
+                         "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode)")
+    ap.add_argument("--out", default=None, help="nearest, neighbours: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -51,6 +54,8 @@ def main():
         return hits_mode(a, md5)
     if a.mode == "nearest":
         return nearest_mode(a, md5)
+    if a.mode == "neighbours":
+        return neighbours_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -302,7 +307,6 @@ def nearest_mode(a, md5):
     kernel_ms from the HIP events around each launch. One JSON line per arm: median / min / max ms, the ratios of the
     medians to the closest query's and (per point) to the exhaustive kernel's, nodes_visited and tris_tested per point,
     the counters, and whether the fast kernel equals the exhaustive one on the 4,096 points."""
-    import numpy as np
     import torch
     from prt import device, host
     W, H, n = a.width, a.height, a.width * a.height
@@ -312,22 +316,7 @@ def nearest_mode(a, md5):
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
         r.upload(s)
-        c = torch.from_numpy(host.camera_array(host.camera(W, H))).cuda()
-        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device="cuda"),
-                                torch.arange(W, dtype=torch.float32, device="cuda"), indexing="ij")
-        d = ((c[1] - c[0])[None, :] + c[2][None, :] * xs.reshape(-1, 1)) + c[3][None, :] * ys.reshape(-1, 1)
-        o = c[0][None, :].expand_as(d).contiguous()
-        g = torch.Generator(device="cpu").manual_seed(1)
-        perm = torch.randperm(n, generator=g).cuda()
-        hit, t = r.trace_rays(o, d, kernel="fast")
-        r.sync()
-        t1 = torch.where(hit >= 0, t, torch.ones_like(t))
-        near = (o + d * (t1 + 0.05)[:, None]).contiguous()
-        co = torch.from_numpy(np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3))
-        lo, hi = co.min(0).values, co.max(0).values
-        grow = (hi - lo) / 4
-        uni = (torch.rand(n, 3, generator=g) * (hi - lo + 2 * grow) + (lo - grow)).cuda().contiguous()
-        sets = [("near_surface", near), ("near_surface_perm", near[perm].contiguous()), ("uniform_box", uni)]
+        o, d, g, sets = point_sets(r, s, W, H)
         for label, pts in sets:
             sample = pts[torch.randperm(n, generator=g)[:NS].cuda()].contiguous()
 
@@ -369,6 +358,96 @@ def nearest_mode(a, md5):
                 if "nodes_visited" in info:
                     line["nodes_visited_per_point"] = round(info["nodes_visited"] / cnt[k], 2)
                     line["tris_tested_per_point"] = round(info["tris_tested"] / cnt[k], 2)
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+        r.close()
+    if out:
+        out.close()
+
+
+def point_sets(r, s, W, H):
+    """the camera's rays (o, d), the generator, and §3p's three sets of W x H points: the primary hit points pushed 0.05
+    along the ray, the same in a fixed random permutation, uniform points in the scene's box grown by a quarter"""
+    import numpy as np
+    import torch
+    from prt import host
+    n = W * H
+    c = torch.from_numpy(host.camera_array(host.camera(W, H))).cuda()
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device="cuda"),
+                            torch.arange(W, dtype=torch.float32, device="cuda"), indexing="ij")
+    d = ((c[1] - c[0])[None, :] + c[2][None, :] * xs.reshape(-1, 1)) + c[3][None, :] * ys.reshape(-1, 1)
+    o = c[0][None, :].expand_as(d).contiguous()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    perm = torch.randperm(n, generator=g).cuda()
+    hit, t = r.trace_rays(o, d, kernel="fast")
+    r.sync()
+    t1 = torch.where(hit >= 0, t, torch.ones_like(t))
+    near = (o + d * (t1 + 0.05)[:, None]).contiguous()
+    co = torch.from_numpy(np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3))
+    lo, hi = co.min(0).values, co.max(0).values
+    grow = (hi - lo) / 4
+    uni = (torch.rand(n, 3, generator=g) * (hi - lo + 2 * grow) + (lo - grow)).cuda().contiguous()
+    return o, d, g, [("near_surface", near), ("near_surface_perm", near[perm].contiguous()), ("uniform_box", uni)]
+
+
+def neighbours_mode(a, md5):
+    """--mode neighbours: per scene, on §3p's three sets of W x H points (point_sets), rt_nearest_tris
+    with k = 1, 4, 8 and 16 (tri, d2 and count), k = 1 and k = 8 with the point output as well, and the pure count
+    within max_dist2 = 1e-3 (k = 0, count_all), beside the unchanged rt_nearest_points on the same points. One untimed
+    round first; then --runs rounds with the arms interleaved; kernel_ms from the HIP events around each launch. One
+    JSON line per arm: median / min / max ms, the ratio of the medians to rt_nearest_points', nodes_visited and
+    tris_tested per point, the counters, and whether the fast kernel equals the exhaustive one on 4,096 of the points
+    (every output the arm writes)."""
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        _, _, g, sets = point_sets(r, s, W, H)
+        radius = torch.full((n,), 1e-3, dtype=torch.float32, device="cuda")
+        for label, pts in sets:
+            sample = pts[torch.randperm(n, generator=g)[:NS].cuda()].contiguous()
+
+            def nearest(p=pts, kernel="fast"):
+                res = r.nearest(p, kernel=kernel)
+                return r.nearest_info(), res
+
+            def tris(k, points_out=False, count=False, p=pts, kernel="fast"):
+                res = r.nearest_tris(p, k=k, points_out=points_out, kernel=kernel, count_all=count,
+                                     max_dist2=radius[:len(p)] if count else None)
+                return r.neighbours_info(), res
+
+            arms = [("nearest_points", nearest), ("tris1", lambda **kw: tris(1, **kw)),
+                    ("tris1_points", lambda **kw: tris(1, True, **kw)), ("tris4", lambda **kw: tris(4, **kw)),
+                    ("tris8", lambda **kw: tris(8, **kw)), ("tris8_points", lambda **kw: tris(8, True, **kw)),
+                    ("tris16", lambda **kw: tris(16, **kw)), ("count_1e-3", lambda **kw: tris(0, count=True, **kw))]
+            same = {}
+            for k, fn in arms:  # the sample against the exhaustive kernel, and the untimed round
+                x, y = fn(p=sample)[1], fn(p=sample, kernel="strict")[1]
+                same[k] = all(bool((p.view(torch.int32) == q.view(torch.int32)).all()) for p, q in zip(x, y))
+                fn()
+            ms, last = {k: [] for k, _ in arms}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k] = fn()[0]
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                line = {"scene": name, "set": label, "arm": k, "points": n, "width": W, "height": H,
+                        "mpoints_s": round(n / med[k] / 1e3, 2), "kernel_ms_median": round(med[k], 4),
+                        "kernel_ms_min": round(min(ms[k]), 4), "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_nearest_points": round(med[k] / med["nearest_points"], 3), "runs": a.runs,
+                        "sample_equals_exhaustive": same[k],
+                        "nodes_visited_per_point": round(info["nodes_visited"] / n, 2),
+                        "tris_tested_per_point": round(info["tris_tested"] / n, 2),
+                        "info": {x: v for x, v in info.items() if x != "kernel_ms"}, "lib_md5": md5}
                 print(json.dumps(line), flush=True)
                 if out:
                     out.write(json.dumps(line) + "\n")
