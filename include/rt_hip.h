@@ -533,6 +533,76 @@ typedef struct rt_neighbours_info {
  * are not valid), RT_E_STATE before the first */
 int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info);
 
+/* Overlap queries: per caller-supplied axis-aligned box the triangles that touch it, and how many -- the query for a
+ * volume (filling a voxel grid, the faces under a moving body's bounds, what a culling cell holds, the cells of a
+ * distance field that lie near the surface).
+ * Query i is the closed box [lo, hi] (a box with lo == hi on one, two or three axes -- a plane, a line, a point -- is
+ * valid). Its answer is
+ *   S_i = { j : T(lo, hi, triangle j) }, ordered by original triangle index ascending,
+ * and S_i is empty when any of the six numbers is non-finite or lo > hi on an axis (decided before any walk). No input
+ * value is an error. T is computed in float32 exactly as follows, on a = v0, e1 = v1 - v0, e2 = v2 - v0 (rounded once,
+ * as the uploaded or updated triangle records hold them), every operation rounded to float32, no FMA. With
+ * b = a + e1 and c = a + e2:
+ *   1. tlo = fminf(fminf(a, b), c); thi = fmaxf(fmaxf(a, b), c)                                   per component
+ *      T is false unless tlo.k <= hi.k && thi.k >= lo.k on all three axes k
+ *   2. T is true if tlo.k >= lo.k && thi.k <= hi.k on all three axes
+ *   3. ctr = 0.5*lo + 0.5*hi;  h = 0.5*hi - 0.5*lo;  v0 = a - ctr; v1 = b - ctr; v2 = c - ctr
+ *      for each edge f of f0 = e1, f1 = e2 - e1, f2 = e2 and each axis k, with i = (k+1)%3, j = (k+2)%3:
+ *        p_m = v_m.j * f.i - v_m.i * f.j   (m = 0, 1, 2);   rad = h.i * |f.j| + h.j * |f.i|
+ *        the axis separates when fminf(fminf(p_0, p_1), p_2) > rad or fmaxf(fmaxf(p_0, p_1), p_2) < -rad
+ *      nrm = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x)
+ *      d = (nrm.x*v0.x + nrm.y*v0.y) + nrm.z*v0.z;   r = (h.x*|nrm.x| + h.y*|nrm.y|) + h.z*|nrm.z|
+ *      the plane separates when |d| > r
+ *      T is true when none of the ten separates (a comparison with a NaN operand separates nothing)
+ * This is Akenine-Moller's triangle-box test behind two exact steps: 1 lets the walk drop a subtree by comparisons
+ * alone, with no margin; 2 reports every triangle inside the box whatever 3 would round to.
+ * Results: tri[i][0..max_tris) receives the first max_tris members of S_i by index (unused slots: -1);
+ * count[i] = min(|S_i|, max_tris), or |S_i| itself with count_all; max_tris = 0 with count_all is a pure count.
+ * The list form (offsets and list given): list[offsets[i] .. offsets[i+1]) receives members of S_i until it is full.
+ * When the segment holds at least |S_i| entries its first |S_i| entries are S_i as a set, in no stated order; the rest
+ * of the segment is not written, and nothing outside it is. count and tri are what they are without a list. A segment
+ * whose end lies below its start, or whose start is negative, has no length. It may be combined with max_tris = 0.
+ * RT_KERNEL_STRICT tests every box against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view and
+ * answers with the same bits; a scene without a wide view (RT_ACCEL_REFERENCE) runs the exhaustive loop under either.
+ * An overlap query touches nothing a render or any other query owns. */
+#define RT_OVERLAPS_MAX 16
+typedef struct rt_boxes {
+    const float* lo;     /* device, [n][3] f32 */
+    const float* hi;     /* device, [n][3] f32 */
+    const int* offsets;  /* device, [n + 1] i32, non-decreasing; nullable: given exactly when rt_overlap_results.list is */
+    int n;               /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;        /* 0..RT_OVERLAPS_MAX */
+    int count_all;       /* 0 / 1 */
+    int kernel;          /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_boxes;
+typedef struct rt_overlap_results { /* device pointers */
+    int* tri;   /* [n][max_tris]; required for max_tris > 0 */
+    int* count; /* [n]; nullable for max_tris > 0, required for max_tris = 0 */
+    int* list;  /* [offsets[n]]; nullable: given exactly when rt_boxes.offsets is */
+} rt_overlap_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, a null lo or hi with n > 0, max_tris outside 0..RT_OVERLAPS_MAX, max_tris > 0 without tri,
+ * max_tris = 0 without count_all and a count pointer, count_all not 0 / 1, offsets without list or list without
+ * offsets, an unknown kernel, a negative n. */
+int rt_overlap_boxes(rt_ctx* ctx, const rt_boxes* boxes, const rt_overlap_results* out);
+typedef struct rt_overlaps_info {
+    long long boxes, found;               /* found: boxes with a non-empty S_i */
+    long long tris_stored, tris_counted;  /* sums of min(|S_i|, max_tris) and of count[i] */
+    long long tris_listed;                /* entries written to list: the sum of min(|S_i|, the segment's length) */
+    long long walked_boxes;               /* boxes that walked the wide view */
+    long long exhaustive_boxes;  /* boxes tested against every triangle: all valid ones under RT_KERNEL_STRICT or without
+                                    a wide view (an invalid box is in neither) */
+    long long empty_boxes;       /* boxes - found */
+    long long nodes_visited;     /* wide nodes decoded, summed over the boxes */
+    long long tris_tested;       /* evaluations of T, summed over the boxes (exhaustive: boxes x triangles; the walk
+                                    takes the triangles of a leaf slot that lies inside the box without one) */
+    long long stack_overflows;   /* must be 0 */
+    float kernel_ms;             /* HIP events around the query's launch */
+} rt_overlaps_info;
+/* counters of the last overlap query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

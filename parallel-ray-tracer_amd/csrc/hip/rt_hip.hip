@@ -36,6 +36,7 @@
 #include "rt_hits.hpp"
 #include "rt_nearest.hpp"
 #include "rt_neighbours.hpp"
+#include "rt_overlap.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -248,6 +249,12 @@ struct rt_ctx {
     bool neighbours_run = false, b_launched = false;
     std::unordered_map<const void*, int> b_resident;  // resident workgroups of each k_neighbours instantiation
     int* d_ref_inv = nullptr;
+    // overlap queries (rt_overlap_boxes, rt_overlap.hpp): their own again ([rtd::O_NCOUNT] counters, then the chunk
+    // counter)
+    unsigned long long* d_ovq = nullptr;
+    hipEvent_t o_ev0 = nullptr, o_ev1 = nullptr;
+    bool overlaps_run = false, o_launched = false;
+    std::unordered_map<const void*, int> o_resident;  // resident workgroups of each k_overlap instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3380,6 +3387,106 @@ extern "C" int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- overlap queries (rt_overlap.hpp)
+namespace {
+using OFn = void (*)(rtd::OArgs);
+// the smallest list capacity that holds max_tris (0: the counting build)
+OFn overlap_kernel(int max_tris, bool strict) {
+    using rtd::k_overlap;
+    if (max_tris == 0) return strict ? k_overlap<0, true> : k_overlap<0, false>;
+    if (max_tris <= 4) return strict ? k_overlap<4, true> : k_overlap<4, false>;
+    if (max_tris <= 8) return strict ? k_overlap<8, true> : k_overlap<8, false>;
+    return strict ? k_overlap<16, true> : k_overlap<16, false>;
+}
+}  // namespace
+
+extern "C" int rt_overlap_boxes(rt_ctx* ctx, const rt_boxes* r, const rt_overlap_results* out) {
+    static_assert(RT_OVERLAPS_MAX == rtd::OVERLAPS_MAX, "rt_hip.h and rt_overlap.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_overlap_boxes: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_overlap_boxes: null boxes / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_overlap_boxes: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_overlap_boxes: negative box count");
+    if (r->max_tris < 0 || r->max_tris > RT_OVERLAPS_MAX) return arg_err(ctx, "rt_overlap_boxes: max_tris must be 0..16");
+    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_overlap_boxes: count_all must be 0 or 1");
+    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_overlap_boxes: max_tris = 0 needs count_all");
+    if ((r->offsets != nullptr) != (out->list != nullptr))
+        return arg_err(ctx, "rt_overlap_boxes: offsets and list are given together or not at all");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->lo || !r->hi)) return arg_err(ctx, "rt_overlap_boxes: null lo / hi");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri) return arg_err(ctx, "rt_overlap_boxes: max_tris > 0 needs a tri output");
+    if (r->n > 0 && r->max_tris == 0 && !out->count)
+        return arg_err(ctx, "rt_overlap_boxes: a counting query needs a count output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::O_NCOUNT + 1);
+    if (!ctx->d_ovq) HIPC(hipMalloc((void**)&ctx->d_ovq, cbytes));
+    if (!ctx->o_ev0) HIPC(hipEventCreate(&ctx->o_ev0));
+    if (!ctx->o_ev1) HIPC(hipEventCreate(&ctx->o_ev1));
+    HIPC(hipMemsetAsync(ctx->d_ovq, 0, cbytes, ctx->stream));
+    ctx->overlaps_run = true;
+    ctx->o_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::OArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.lo = r->lo;
+    A.hi = r->hi;
+    A.offsets = r->offsets;
+    A.tri = r->max_tris > 0 ? out->tri : nullptr;
+    A.count = out->count;
+    A.list = out->list;
+    A.counters = ctx->d_ovq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_ovq + rtd::O_NCOUNT);
+    A.n = r->n;
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    const OFn k = overlap_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->o_resident.find((const void*)k);
+    if (res == ctx->o_resident.end()) res = ctx->o_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->o_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->o_ev1, ctx->stream));
+    ctx->o_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->overlaps_run) {
+        ctx->err = "rt_get_overlaps_info: no overlap query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::O_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_ovq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->boxes = (long long)c[rtd::O_BOXES];
+    info->found = (long long)c[rtd::O_FOUND];
+    info->tris_stored = (long long)c[rtd::O_STORED];
+    info->tris_counted = (long long)c[rtd::O_COUNTED];
+    info->tris_listed = (long long)c[rtd::O_LISTED];
+    info->walked_boxes = (long long)c[rtd::O_WALKED];
+    info->exhaustive_boxes = (long long)c[rtd::O_EXH];
+    info->empty_boxes = (long long)c[rtd::O_EMPTY];
+    info->nodes_visited = (long long)c[rtd::O_NODES];
+    info->tris_tested = (long long)c[rtd::O_TRIS];
+    info->stack_overflows = (long long)c[rtd::O_ERR];
+    if (ctx->o_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->o_ev0, ctx->o_ev1));
+    if (c[rtd::O_ERR]) {
+        ctx->err = "rt_get_overlaps_info: the query's traversal stack overflowed " + std::to_string(c[rtd::O_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4242,6 +4349,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_nbq) (void)hipFree(ctx->d_nbq);
     if (ctx->b_ev0) (void)hipEventDestroy(ctx->b_ev0);
     if (ctx->b_ev1) (void)hipEventDestroy(ctx->b_ev1);
+    if (ctx->d_ovq) (void)hipFree(ctx->d_ovq);
+    if (ctx->o_ev0) (void)hipEventDestroy(ctx->o_ev0);
+    if (ctx->o_ev1) (void)hipEventDestroy(ctx->o_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

@@ -193,6 +193,27 @@ class NeighboursInfo(ctypes.Structure):  # rt_neighbours_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+OVERLAPS_MAX = 16  # RT_OVERLAPS_MAX
+
+
+class Boxes(ctypes.Structure):  # rt_boxes
+    _fields_ = [("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("max_tris", ctypes.c_int), ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class OverlapResults(ctypes.Structure):  # rt_overlap_results
+    _fields_ = [("tri", ctypes.c_void_p), ("count", ctypes.c_void_p), ("list", ctypes.c_void_p)]
+
+
+class OverlapsInfo(ctypes.Structure):  # rt_overlaps_info
+    _fields_ = [("boxes", ctypes.c_longlong), ("found", ctypes.c_longlong), ("tris_stored", ctypes.c_longlong),
+                ("tris_counted", ctypes.c_longlong), ("tris_listed", ctypes.c_longlong),
+                ("walked_boxes", ctypes.c_longlong), ("exhaustive_boxes", ctypes.c_longlong),
+                ("empty_boxes", ctypes.c_longlong), ("nodes_visited", ctypes.c_longlong),
+                ("tris_tested", ctypes.c_longlong), ("stack_overflows", ctypes.c_longlong),
+                ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -318,6 +339,8 @@ def hip():
         L.rt_get_nearest_info.argtypes = [ctypes.c_void_p, P(NearestInfo)]
         L.rt_nearest_tris.argtypes = [ctypes.c_void_p, P(Neighbours), P(NeighbourResults)]
         L.rt_get_neighbours_info.argtypes = [ctypes.c_void_p, P(NeighboursInfo)]
+        L.rt_overlap_boxes.argtypes = [ctypes.c_void_p, P(Boxes), P(OverlapResults)]
+        L.rt_get_overlaps_info.argtypes = [ctypes.c_void_p, P(OverlapsInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

@@ -602,6 +602,99 @@ class Renderer:
         self._chk(_L.rt_get_neighbours_info(self._ctx, ctypes.byref(i)), "rt_get_neighbours_info")
         return {f: getattr(i, f) for f, _ in _lib.NeighboursInfo._fields_}
 
+    def _boxes(self, lo, hi):
+        """(lo pointer, hi pointer, n) of two [n, 3] float32 contiguous tensors on this device, or of raw pointers
+        given as lo=(pointer, n), hi=pointer"""
+        import torch
+        if isinstance(lo, tuple):
+            pl, n = lo
+            if not isinstance(pl, int) or not isinstance(n, int) or n < 0 or not isinstance(hi, int):
+                raise RtError("boxes: raw pointers are given as lo=(pointer, n), hi=pointer")
+            return pl, hi, n
+        for x, what in ((lo, "lo"), (hi, "hi")):
+            if not isinstance(x, torch.Tensor):
+                raise RtError(f"{what}: expected a torch tensor or raw pointers, got {type(x).__name__}")
+            if x.dim() != 2 or x.shape[1] != 3:
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, 3]")
+        n = lo.shape[0]
+        if hi.shape[0] != n:
+            raise RtError(f"hi: {hi.shape[0]} boxes, lo has {n}")
+        f32 = (torch.float32,)
+        return _ptr(lo, "lo", 3 * n, f32, self.device), _ptr(hi, "hi", 3 * n, f32, self.device), n
+
+    def overlaps(self, lo, hi, k=8, count_all=False, kernel="auto", tri=None, count=None):
+        """rt_overlap_boxes: per closed axis-aligned box [lo, hi] the triangles of the scene that touch it -- the first k
+        by original triangle index of S_i = { j : T(lo, hi, triangle j) }, T the float32 triangle-box test
+        include/rt_hip.h states -> (tri [n, k] int32, -1 in unused slots; count [n] int32 = min(|S_i|, k), or |S_i|
+        itself with count_all=True). lo, hi: [n, 3] float32 contiguous tensors on this device (or raw pointers:
+        lo=(pointer, n), hi=pointer). A box with lo == hi on some axes (a plane, a line, a point) is valid; a
+        non-finite number or lo > hi on an axis gives the empty set. k: 0..16; 0 with count_all=True is a pure count
+        (tri comes back empty). kernel="strict" tests every triangle (the checker), "fast" / "auto" walks the full wide
+        view with the same answer. tri / count: optional outputs (allocated when not given). overlaps_csr gives every
+        box's full set. Asynchronous on the renderer's stream: sync() or overlaps_info() before the results are read on
+        another stream."""
+        import torch
+        i32 = (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.OVERLAPS_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.OVERLAPS_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        pl, ph, n = self._boxes(lo, hi)
+        for x, what, m in ((tri, "tri", n * k), (count, "count", n)):
+            _ptr(x, what, m, i32, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        res = _lib.OverlapResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                                  _ptr(count, "count", n, i32, self.device), None)
+        q = _lib.Boxes(pl, ph, None, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_overlap_boxes(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_overlap_boxes")
+        return tri, count
+
+    def overlaps_info(self):
+        """rt_get_overlaps_info: the last overlap query's counters (boxes, found, tris_stored, tris_counted,
+        tris_listed, walked_boxes, exhaustive_boxes, empty_boxes, nodes_visited, tris_tested) and kernel_ms;
+        synchronises; raises when the query overflowed its stack"""
+        i = _lib.OverlapsInfo()
+        self._chk(_L.rt_get_overlaps_info(self._ctx, ctypes.byref(i)), "rt_get_overlaps_info")
+        return {f: getattr(i, f) for f, _ in _lib.OverlapsInfo._fields_}
+
+    def overlaps_csr(self, lo, hi, kernel="auto"):
+        """every box's full S_i, in index order -> (offsets [n + 1] int32, tris [offsets[n]] int32): box i's triangles
+        are tris[offsets[i]:offsets[i + 1]], ascending. Two launches of rt_overlap_boxes -- a pure count, then the list
+        form into the counts' prefix sums -- and one sort that puts each segment in order (the list form states none).
+        Synchronises (the total is read on the host); refuses a total of 2^31 or more. lo, hi and kernel as overlaps
+        takes them."""
+        import torch
+        pl, ph, n = self._boxes(lo, hi)
+        dev = f"cuda:{self.device}"
+        kern = KERNELS.get(kernel, kernel)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        q = _lib.Boxes(pl, ph, None, n, 0, 1, kern)
+        res = _lib.OverlapResults(None, _ptr(count, "count", n, (torch.int32,), self.device), None)
+        self._chk(_L.rt_overlap_boxes(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_overlap_boxes")
+        self.overlaps_info()  # (synchronises the renderer's stream with torch's; raises on an overflowed stack)
+        ends = torch.cumsum(count, 0, dtype=torch.int64)
+        total = int(ends[-1]) if n else 0
+        if total >= 2 ** 31:
+            raise RtError(f"overlaps_csr: {total} entries in all, int32 offsets hold fewer than 2^31: split the boxes")
+        offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        offsets[1:] = ends.to(torch.int32)
+        tris = torch.empty(total, dtype=torch.int32, device=dev)
+        if total == 0:
+            return offsets, tris
+        torch.cuda.current_stream(self.device).synchronize()  # (offsets is torch's work, the query runs on ours)
+        q = _lib.Boxes(pl, ph, offsets.data_ptr(), n, 0, 1, kern)
+        res = _lib.OverlapResults(None, count.data_ptr(), tris.data_ptr())
+        self._chk(_L.rt_overlap_boxes(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_overlap_boxes")
+        self.overlaps_info()
+        n_tris = self.scene_info()["n_triangles"]
+        seg = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), count.to(torch.int64))
+        key, _ = torch.sort(seg * n_tris + tris.to(torch.int64))  # (segment-major, index ascending within each)
+        return offsets, (key - seg * n_tris).to(torch.int32)
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

@@ -13,12 +13,14 @@ and, for context beside primary_rows, the frame kernel's own rate (stats()["rays
 The fast and the strict kernel answer with the same bits (checked here on every set).
 --mode shade times rt_shade_rays instead (shade_mode below), --mode hits rt_trace_hits beside the
 closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below),
---mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below).
+--mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below), --mode overlap
+rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
        python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -35,12 +37,14 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours"], default="trace",
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap"],
+                    default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
                          "nearest: rt_nearest_points beside the closest-hit query (nearest_mode); "
-                         "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode)")
-    ap.add_argument("--out", default=None, help="nearest, neighbours: also append the raw lines to this file")
+                         "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode); "
+                         "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode)")
+    ap.add_argument("--out", default=None, help="nearest, neighbours, overlap: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -56,6 +60,8 @@ def main():
         return nearest_mode(a, md5)
     if a.mode == "neighbours":
         return neighbours_mode(a, md5)
+    if a.mode == "overlap":
+        return overlap_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -452,6 +458,108 @@ def neighbours_mode(a, md5):
                 if out:
                     out.write(json.dumps(line) + "\n")
                     out.flush()
+        r.close()
+    if out:
+        out.close()
+
+
+def overlap_mode(a, md5):
+    """--mode overlap: per scene, rt_overlap_boxes on W x H boxes (1920 x 1080 = 2,073,600 by default)
+    in two shapes: cubes centred on the hit points of the camera's primary rays (a missing ray's centre lies at t = 1)
+    with half-widths of 0.1 %, 1 % and 5 % of the scene's extent (its box's longest side), and a voxel grid over the
+    scene's box (prt.boxes.grid; 128 x 135 x 120 cells at the default size). Per set: the pure count (k = 0,
+    count_all), k = 8 (tri and count) and the CSR form (overlaps_csr: the count, the list form and the sort; wall-clock
+    ms around the call, skipped when the sets hold more than 2^27 entries in all), beside rt_nearest_tris' pure
+    count within the same half-width on the same centres (a ball inside the cube: fewer triangles), and the
+    exhaustive kernel's count and k = 8 on 4,096 of the boxes. One untimed round first; then --runs rounds with the
+    arms interleaved; kernel_ms from the HIP events around each launch. One JSON line per arm: median / min / max ms,
+    the per-box ratio to the exhaustive kernel, nodes_visited and tris_tested per box, the counters, and whether the
+    fast kernel equals the exhaustive one on the 4,096 boxes."""
+    import time
+
+    import numpy as np
+    import torch
+    from prt import boxes, device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS, CSR_CAP = 4096, 1 << 27
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        o, d, g, _ = point_sets(r, s, W, H)
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        ctr = (o + d * torch.where(hit >= 0, t, torch.ones_like(t))[:, None]).contiguous()
+        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+        slo, shi = v.min(0), v.max(0)
+        ext = float((shi - slo).max())
+        dims = (128, 135, 120) if n == 2073600 else (W, H, 1)
+        glo, ghi = boxes.grid(slo, shi, dims)
+        sets = [(f"hit_points_{pct}pct", (ctr - ext * pct / 100).contiguous(), (ctr + ext * pct / 100).contiguous(), ctr,
+                 ext * pct / 100) for pct in (0.1, 1.0, 5.0)]
+        cell = float(((shi - slo) / np.array(dims, np.float32)).max()) / 2
+        sets.append((f"grid_{dims[0]}x{dims[1]}x{dims[2]}", glo, ghi, ((glo + ghi) * 0.5).contiguous(), cell))
+        for label, lo, hi, centres, radius in sets:
+            pick = torch.randperm(n, generator=g)[:NS].cuda()
+            slo_, shi_ = lo[pick].contiguous(), hi[pick].contiguous()
+            md = torch.full((n,), radius * radius, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+
+            def boxes_arm(k, l=lo, h=hi, kernel="fast"):
+                res = r.overlaps(l, h, k=k, count_all=k == 0, kernel=kernel)
+                return r.overlaps_info(), res, len(l)
+
+            def ball_count():
+                res = r.nearest_tris(centres, k=0, count_all=True, max_dist2=md)
+                return r.neighbours_info(), res, n
+
+            def csr():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = r.overlaps_csr(lo, hi)
+                torch.cuda.synchronize()
+                info = dict(r.overlaps_info())
+                info["kernel_ms"] = (time.perf_counter() - t0) * 1e3  # (wall clock: two launches, a scan and a sort)
+                return info, res, n
+
+            total = int(boxes_arm(0)[1][1].sum(dtype=torch.int64))
+            arms = [("count", lambda: boxes_arm(0)), ("k8", lambda: boxes_arm(8)), ("ball_count", ball_count),
+                    ("count_exhaustive_4096", lambda: boxes_arm(0, slo_, shi_, "strict")),
+                    ("k8_exhaustive_4096", lambda: boxes_arm(8, slo_, shi_, "strict"))]
+            if total <= CSR_CAP:
+                arms.append(("csr", csr))
+            same = {}
+            for k in (0, 8):  # the sample against the exhaustive kernel
+                x, y = boxes_arm(k, slo_, shi_)[1], boxes_arm(k, slo_, shi_, "strict")[1]
+                same["count" if k == 0 else "k8"] = all(bool((p == q).all()) for p, q in zip(x, y))
+            for _, fn in arms:  # the untimed round
+                fn()
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _, cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                exh = "k8_exhaustive_4096" if k.startswith("k8") else "count_exhaustive_4096"
+                line = {"scene": name, "set": label, "arm": k, "boxes": cnt[k], "half_width": round(radius, 6),
+                        "set_entries": total, "mboxes_s": round(cnt[k] / med[k] / 1e3, 2),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "per_box_ratio_to_exhaustive": round((med[k] / cnt[k]) / (med[exh] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same.get(k),
+                        "nodes_visited_per_box": round(info["nodes_visited"] / cnt[k], 2),
+                        "tris_tested_per_box": round(info["tris_tested"] / cnt[k], 2),
+                        "info": {x: v for x, v in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+            if total > CSR_CAP:
+                print(json.dumps({"scene": name, "set": label, "arm": "csr", "skipped": "set_entries above the cap",
+                                  "set_entries": total, "cap": CSR_CAP}), flush=True)
         r.close()
     if out:
         out.close()
