@@ -39,7 +39,11 @@ enum {
      * scenes of test size (tests/test_gpu_unpacked.py). The result is bit-identical either way. */
     RT_FLAG_UNPACKED_STACK = 2, /* as for a scene of more than 2^24 wide nodes: no packed stack entries (no pool
                                    kernels, PERSIST4 with two-word entries) */
-    RT_FLAG_UNPACKED_TRIS = 4   /* as for a scene of 2^26 or more triangles: no packed triangle tests */
+    RT_FLAG_UNPACKED_TRIS = 4,  /* as for a scene of 2^26 or more triangles: no packed triangle tests */
+    /* The pool kernels hand their shadow rays out from a per-wave job list in LDS where it fits 4 workgroups per CU,
+     * and with a cursor where it does not (many lights, 5-8 bounces, deep trees). This flag selects the cursor for any
+     * scene, so that it can be checked on scenes of test size (tests/test_gpu_pool_handout.py). Same bits, same walks. */
+    RT_FLAG_POOL_CURSOR = 8     /* as for a launch whose LDS has no room for the job lists */
 };
 
 typedef struct rt_opts {
@@ -273,8 +277,9 @@ enum {
     RT_BUILD_POOL_LEVEL = 16,  /* the per-level shadow pool (RT_VARIANT_SHPOOL) */
     RT_BUILD_POOL_ALL = 32,    /* one shadow pool for all levels (RT_VARIANT_SHDEFER) */
     RT_BUILD_TRACE = 64,       /* the measuring build with per-tile times */
-    RT_BUILD_FEEDBACK = 128    /* a decided single-frame shape's frame dealt by the previous frame's per-tile times, its
+    RT_BUILD_FEEDBACK = 128,   /* a decided single-frame shape's frame dealt by the previous frame's per-tile times, its
                                   tile lists built on the device (no measuring frames, no host round trip) */
+    RT_BUILD_POOL_LIST = 256   /* a pool kernel handing its rays out from the per-wave job list (else its cursor) */
 };
 int rt_get_launch_info(rt_ctx* ctx, rt_launch_info* info);
 

@@ -14,7 +14,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -123,6 +125,7 @@ struct rt_ctx {
     // the packed builds' bounds: 5-byte stack entries hold a 24-bit child base (rtd::WIDE_MAX_NODES wide nodes per
     // view), packed triangle-test jobs a 26-bit triangle (rtd::TQ_MAX_TRIS); larger scenes run the unpacked builds
     bool pk_ok = true, tq_ok = true;
+    bool list_ok = true;  // the pool kernels may take their job-list hand-out (off: RT_FLAG_POOL_CURSOR)
     float amb[3] = {0.5f, 0.5f, 0.5f};
     // every face coordinate of the reference tree's child boxes, per axis, sorted, one axis after another
     // (rtd::DScene::faces; n_face below)
@@ -547,6 +550,7 @@ extern "C" int rt_create(const rt_opts* opts, rt_ctx** out) {
     if (opts) {
         ctx->device = opts->device;
         ctx->flags = opts->flags;
+        ctx->list_ok = !(opts->flags & RT_FLAG_POOL_CURSOR);
         ctx->stream = (hipStream_t)opts->stream;
     }
     if (ctx->device < 0 || ctx->device >= n) {
@@ -1117,10 +1121,19 @@ using KFn = void (*)(rtd::KArgs);
 // the 4-wave k_persist instantiation of a launch: path buffer in LDS (pbl) or global memory, the spp = 1 build,
 // counters; SHP: the per-wave shadow pool (rt_shpool.hpp; 1: one pool per level, 2: one for all levels), which needs
 // the LDS path buffer
+// list (the pool kernels): the pool's job-list hand-out (its LDS sized by pbl_bytes), else the cursor's
 template <int MAXB, int SHP>
-KFn persist4(bool pbl, bool spp1, bool count) {
+KFn persist4(bool pbl, bool spp1, bool count, bool list = false) {
     using rtd::k_persist;
     if (pbl) {
+        if constexpr (SHP == 1 || SHP == 2) {
+            if (!list) {
+                if (spp1) return count ? k_persist<MAXB, false, true, true, 4, false, true, 2, true, true, SHP, false>
+                                       : k_persist<MAXB, false, false, true, 4, false, true, 2, true, true, SHP, false>;
+                return count ? k_persist<MAXB, false, true, true, 4, false, true, 2, true, false, SHP, false>
+                             : k_persist<MAXB, false, false, true, 4, false, true, 2, true, false, SHP, false>;
+            }
+        }
         if (spp1) return count ? k_persist<MAXB, false, true, true, 4, false, true, 2, true, true, SHP>
                                : k_persist<MAXB, false, false, true, 4, false, true, 2, true, true, SHP>;
         return count ? k_persist<MAXB, false, true, true, 4, false, true, 2, true, false, SHP>
@@ -1147,22 +1160,40 @@ rtd::KArgs with_slots(const rtd::KArgs& A, size_t dyn) {
 // dynamic LDS of the 4-wave kernels' LDS layout: the wide stack sized to the scene's wide depth, then the path levels
 // (and, for the all-levels pool, each level's hit triangle)
 // (and, for spp > 1, the lanes' sample-sum slots at the end: rtd::KArgs::slot_off)
+// (and, for a pool kernel with the job-list hand-out, the waves' lists after the queues: rt_pool_list.hpp)
 template <int MAXB>
-size_t pbl_bytes(const rtd::KArgs& A, int shp = 0) {
+size_t pbl_bytes(const rtd::KArgs& A, int shp = 0, bool list = false) {
+    const size_t jl = list && (shp == 1 || shp == 2)
+                          ? sizeof(int) * (rtd::BLOCK / 64) * (size_t)rtp::list_words(shp == 2 ? MAXB : 1, A.s.n_lights)
+                          : 0;
     return sizeof(int) * (size_t)rtd::wstack_words(A.wcap, shp > 0) * rtd::BLOCK + sizeof(float4) * rtd::BLOCK * MAXB +
            (shp == 2 ? sizeof(int) * (rtd::BLOCK * MAXB + rtd::BLOCK / 64 * rtd::TQ_WORDS) : 0) +
-           (shp == 1 || shp == 3 ? sizeof(int) * (rtd::BLOCK / 64 * rtd::TQ_WORDS) : 0) + slot_bytes(A);
+           (shp == 1 || shp == 3 ? sizeof(int) * (rtd::BLOCK / 64 * rtd::TQ_WORDS) : 0) + jl + slot_bytes(A);
 }
 // Does that layout fit 4 workgroups per CU for this scene? (the LDS path buffer measured 1.2 % faster than the global
 // slab on dragon, 2.3 % on car_boxed; the shadow pool needs it)
 template <int MAXB>
-bool pbl_fits(const rtd::KArgs& A, int device, int shp = 0) {
+bool pbl_fits(const rtd::KArgs& A, int device, int shp = 0, bool list = false) {
     if (!A.gstack || A.wcap <= 0) return false;
-    (void)device;
+    // asked once per (device, layout size): the query runs between a launch's start event and its kernel, and the
+    // list's extra question must not count against the pool in the batch rule's trials (a process-wide memo; contexts
+    // may be driven from distinct threads)
+    static std::mutex mx;
+    static std::map<std::pair<int, size_t>, bool> memo;
+    const size_t bytes = pbl_bytes<MAXB>(A, shp, list);
+    const std::pair<int, size_t> key(device, bytes);
+    {
+        std::lock_guard<std::mutex> g(mx);
+        const auto it = memo.find(key);
+        if (it != memo.end()) return it->second;
+    }
     int per_cu = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist4<MAXB, 0>(true, true, false), rtd::BLOCK,
-                                                        pbl_bytes<MAXB>(A, shp)) == hipSuccess &&
-           per_cu >= 4;
+    const bool fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist4<MAXB, 0>(true, true, false),
+                                                                   rtd::BLOCK, bytes) == hipSuccess &&
+                      per_cu >= 4;
+    std::lock_guard<std::mutex> g(mx);
+    memo[key] = fits;
+    return fits;
 }
 bool pbl_fits(const rtd::KArgs& A, int device, int shp) { return FOR_MAXB(A.bounces, pbl_fits, A, device, shp); }
 
@@ -1195,7 +1226,7 @@ KFn coop_kernel(int bounces, int G, bool count) { return FOR_MAXB(bounces, coop_
 // per-tile timestamps.
 template <int MAXB>
 KFn persist_kernel_of(const rtd::KArgs& A, int variant, bool count, int device, size_t& dyn, bool pk_ok, bool tq_ok,
-                      unsigned* build) {
+                      bool list_ok, unsigned* build) {
     dyn = 0;
     unsigned bd = 0;  // rt_launch_info.build of the instantiation returned (RT_BUILD_*)
     struct Report {
@@ -1215,10 +1246,14 @@ KFn persist_kernel_of(const rtd::KArgs& A, int variant, bool count, int device, 
     if ((variant == RT_VARIANT_SHPOOL || variant == RT_VARIANT_SHDEFER) && pk_ok && tq_ok) {
         const int shp = variant == RT_VARIANT_SHDEFER ? 2 : 1;
         if (pbl_fits<MAXB>(A, device, shp)) {
-            dyn = pbl_bytes<MAXB>(A, shp);
+            // the job-list hand-out where its lists fit too (dragon, car_boxed, two_cars: 1-4 KB per workgroup), else
+            // the cursor's (many lights, MAXB = 8, deep stacks; RT_FLAG_POOL_CURSOR)
+            const bool list = list_ok && pbl_fits<MAXB>(A, device, shp, true);
+            dyn = pbl_bytes<MAXB>(A, shp, list);
             bd = RT_BUILD_WAVES4 | RT_BUILD_PACKED_STACK | RT_BUILD_PACKED_TRIS | RT_BUILD_LDS_PATHS |
-                 (shp == 2 ? RT_BUILD_POOL_ALL : RT_BUILD_POOL_LEVEL);
-            return shp == 2 ? persist4<MAXB, 2>(true, A.spp <= 1, count) : persist4<MAXB, 1>(true, A.spp <= 1, count);
+                 (shp == 2 ? RT_BUILD_POOL_ALL : RT_BUILD_POOL_LEVEL) | (list ? RT_BUILD_POOL_LIST : 0u);
+            return shp == 2 ? persist4<MAXB, 2>(true, A.spp <= 1, count, list)
+                            : persist4<MAXB, 1>(true, A.spp <= 1, count, list);
         }
     }
     // PERSIST4 with packed stack entries and packed triangle tests (SHP = 3) where its LDS fits: sportscar 20-frame
@@ -1252,15 +1287,15 @@ KFn persist_kernel_of(const rtd::KArgs& A, int variant, bool count, int device, 
 }
 
 KFn persist_kernel(const rtd::KArgs& A, int variant, bool count, int device, size_t& dyn, bool pk_ok, bool tq_ok,
-                   unsigned* build = nullptr) {
-    return FOR_MAXB(A.bounces, persist_kernel_of, A, variant, count, device, dyn, pk_ok, tq_ok, build);
+                   bool list_ok, unsigned* build = nullptr) {
+    return FOR_MAXB(A.bounces, persist_kernel_of, A, variant, count, device, dyn, pk_ok, tq_ok, list_ok, build);
 }
 
 // `cap`: workgroups per CU at most (0: the occupancy limit); the grid never exceeds the tiles / 4.
 void launch_paths(const rtd::KArgs& A, int variant, bool count, int device, hipStream_t s, int cap, bool pk_ok,
-                  bool tq_ok, unsigned* build = nullptr) {
+                  bool tq_ok, bool list_ok, unsigned* build = nullptr) {
     size_t dyn = 0;
-    const KFn k = persist_kernel(A, variant, count, device, dyn, pk_ok, tq_ok, build);
+    const KFn k = persist_kernel(A, variant, count, device, dyn, pk_ok, tq_ok, list_ok, build);
     const int blocks = std::max(1, std::min(resident(k, device, cap > 0 ? cap : 8, dyn), (A.n_tiles * A.n_frames + 3) / 4));
     k<<<blocks, rtd::BLOCK, dyn, s>>>(with_slots(A, dyn));
 }
@@ -1805,7 +1840,7 @@ int launch_hybrid(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsigned*
     P.region_off = h.cold_regions ? lists + n_hot : nullptr;
     P.tile_order = lists + n_hot + (h.cold_regions ? 9 : 0);
     size_t dyn = 0;
-    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
+    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, ctx->list_ok, build);
     const int rp = resident(kp, ctx->device, 8, dyn);
     const int rcp = resident(kc, ctx->device);
     int nc, np;
@@ -1887,7 +1922,7 @@ int launch_hybrid_fb(rt_ctx* ctx, const rtd::KArgs& A, bool count, int c, unsign
     P.tile_order = d_cold + 9;
     P.tile_cost = cost_out;
     size_t dyn = 0;
-    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, build);
+    const KFn kp = persist_kernel(P, h.cand[c].cold, count, ctx->device, dyn, ctx->pk_ok, ctx->tq_ok, ctx->list_ok, build);
     if (build) *build |= RT_BUILD_FEEDBACK;
     const int rp = resident(kp, ctx->device, 8, dyn);
     const int rcp = resident(kc, ctx->device);
@@ -1953,7 +1988,7 @@ int dispatch_hybrid(rt_ctx* ctx, Launch& L, int cp, rtd::KArgs& P) {
         li.trial = li.refresh ? 0 : 1;
         li.settled = li.refresh;
         P.tile_trace = h.d_tr;
-        launch_paths(P, RT_VARIANT_PERSIST, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
+        launch_paths(P, RT_VARIANT_PERSIST, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, ctx->list_ok, &li.build);
         HIPC(hipGetLastError());
         HIPC(hipMemcpyAsync(h.h_tr, h.d_tr, sizeof(unsigned long long) * 4 * h.n_tiles, hipMemcpyDeviceToHost,
                             ctx->stream));
@@ -1963,7 +1998,7 @@ int dispatch_hybrid(rt_ctx* ctx, Launch& L, int cp, rtd::KArgs& P) {
     }
     // a whole-frame kernel: chosen, tried, or while the measurement / trials are on their way
     li.variant = pk.c;
-    launch_paths(P, pk.c, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &li.build);
+    launch_paths(P, pk.c, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, ctx->list_ok, &li.build);
     return RT_OK;
 }
 
@@ -1997,7 +2032,7 @@ int dispatch(rt_ctx* ctx, Launch& L, int md, int cp) {
         P.tile_order = L.region_order;
     }
     if (md == RT_VARIANT_HYBRID) return dispatch_hybrid(ctx, L, cp, P);
-    launch_paths(P, md, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, &L.li.build);
+    launch_paths(P, md, L.count, ctx->device, ctx->stream, cp, ctx->pk_ok, ctx->tq_ok, ctx->list_ok, &L.li.build);
     return RT_OK;
 }
 

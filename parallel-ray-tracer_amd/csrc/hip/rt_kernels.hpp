@@ -174,6 +174,17 @@ __device__ __forceinline__ float shadow_reach(v3 o, float ld2) {
     const float om = fmaxf(fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
     return __builtin_sqrtf(ld2) * 1.001f + om * 1e-5f;
 }
+// shadow_reach for a caller that holds sqrtf(ld2) already: the shadow pool's ray formation has it as the length mg
+// of the light vector it normalises (rt_shpool.hpp states why the two are the same bits). PRT_REACH_MAG=0: the pool
+// recomputes the root.
+#ifndef PRT_REACH_MAG
+#define PRT_REACH_MAG 1
+#endif
+constexpr bool REACH_MAG = PRT_REACH_MAG != 0;
+__device__ __forceinline__ float shadow_reach_mag(v3 o, float mg) {
+    const float om = fmaxf(fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z));
+    return mg * 1.001f + om * 1e-5f;
+}
 
 // ---------------------------------------------------------------- one interior node
 // Entry distances of both children of record `ref`, nearer child first (empty child / miss: FMAX).
@@ -463,7 +474,7 @@ __device__ __forceinline__ void count_step(Ctr& c, bool shadow) {
     const unsigned b = ((unsigned)__builtin_popcountll(ex) - 1u) >> 4;
     c.ws += f;
     if (shadow) c.wsh += f;
-#ifndef PRT_DIAG_TRI
+#if !defined(PRT_DIAG_TRI) && !defined(PRT_DIAG_REFILL)
     c.q1 += b == 0 ? f : 0u;
     c.q2 += b == 1 ? f : 0u;
     c.q3 += b == 2 ? f : 0u;
@@ -1647,7 +1658,7 @@ __device__ __forceinline__ float4* lane_slot(const KArgs& A) {
 
 // the shadow-pool kernels' pixel (rt_shpool.hpp, RT_VARIANT_SHPOOL): every lane of the wave calls it
 struct UCtr;
-template <int MAXB, bool COUNT, bool SPP1, int SHP>
+template <int MAXB, bool COUNT, bool SPP1, int SHP, bool JL>
 __device__ __forceinline__ void render_pixel_shp(const KArgs& A, const Cam& C, int frame, int x, int k, bool valid,
                                                  int* __restrict__ stk, Ctr& c, UCtr& u, int* __restrict__ sstk,
                                                  int wcap);
@@ -1807,9 +1818,12 @@ template <> struct UCtrSel<3> { struct type {}; };
 template <int SHP> using UCtrOf = typename UCtrSel<SHP>::type;
 
 template <int MAXB, bool STRICT, bool COUNT, bool REG = true, int OCC = 3, bool TRACE = false, bool BATCH = false,
-          int PB = 0, bool DYN = false, bool SPP1 = false, int SHP = 0>
+          int PB = 0, bool DYN = false, bool SPP1 = false, int SHP = 0, bool JL = (SHP == 1 || SHP == 2)>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, BLOCK), amdgpu_waves_per_eu(OCC > 0 ? OCC : 1)))
 void k_persist(KArgs A) {
+    // JL (the pool kernels, SHP 1 / 2): the pool's rays handed out from a per-wave job list in LDS after the queues
+    // (rt_shpool.hpp shadow_pool<.., LIST>; false: the cursor hand-out, for launches whose LDS has no room for it)
+    static_assert(!JL || SHP == 1 || SHP == 2, "the job list belongs to the pool kernels");
     static_assert(PB != 2 || DYN, "an LDS path buffer lives in the DYN kernels' dynamic LDS");
     static_assert(SHP == 0 || SHP == 3 || PB == 2, "the shadow pool hands its rays over through the LDS path buffer");
     // SHP = 3: no pool; packed triangle tests (queues after the LDS path buffer with packed stack entries in the DYN
@@ -1879,7 +1893,7 @@ void k_persist(KArgs A) {
         const unsigned fb0 = c.fb, ws0 = c.ws, nd0 = c.chi + c.shi;
         if (TRACE || A.tile_cost) t0 = __builtin_amdgcn_s_memrealtime();
         if constexpr (SHP == 1 || SHP == 2)
-            render_pixel_shp<MAXB, COUNT, SPP1, SHP>(A, cam_of<BATCH>(A, frame), frame, x, k, x < A.W && k < A.n_rows,
+            render_pixel_shp<MAXB, COUNT, SPP1, SHP, JL>(A, cam_of<BATCH>(A, frame), frame, x, k, x < A.W && k < A.n_rows,
                                                      stk, c, u, sstk, wcap);
         else if (x < A.W && k < A.n_rows)
             render_pixel<MAXB, STRICT, COUNT, REG, 1, PB, SPP1 ? 1 : 2, SHP == 3, SHP == 3 && DYN>(

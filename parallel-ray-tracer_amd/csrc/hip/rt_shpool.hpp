@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "rt_kernels.hpp"
+#include "rt_pool_list.hpp"
 
 namespace rtd {
 
@@ -27,6 +28,24 @@ __device__ __forceinline__ unsigned long long uni64(unsigned long long v) {
     return ((unsigned long long)hi << 32) | lo;
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// this lane's rank among the set bits of the wave mask m: the set bits below the lane's own
+__device__ __forceinline__ unsigned mbcnt64(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// Diagnostics build (PRT_DEFS=-DPRT_DIAG_REFILL): under RT_FLAG_COUNTERS the lane-count bins count the pool's refill
+// instead of wave steps -- q1 refill rounds, q2 iterations of the cursor hand-out's loop (the list form has none),
+// q3 lanes refilled, q4 job lists built (tools/stream_budget.py prices them).
+#ifdef PRT_DIAG_REFILL
+#define PRT_REFILL_CNT(c, q, n) \
+    do {                        \
+        if (COUNT) (c).q += (n); \
+    } while (0)
+#else
+#define PRT_REFILL_CNT(c, q, n) \
+    do {                        \
+    } while (0)
+#endif
 
 // position of the k-th (0-based) set bit of m (k < popcount(m)): a binary search over popcounts, on scalar registers
 // for a wave-uniform (m, k), per lane otherwise
@@ -88,10 +107,20 @@ __device__ __forceinline__ void flush_u(const UCtr& u, unsigned long long* g) {
 // and 0 in its .w, and the walkers set bit j of that .w (as an unsigned) when light j is visible from it along the
 // reference's shadow ray. regroup: idle lanes that trigger a refill (all lanes idle always do). Called by every lane
 // of the wave.
-template <bool COUNT, int LV, bool TQ = false, class OKM>
+//
+// The hand-out. Which idle lane takes which ray is one rule in two forms: the k-th idle lane (lane order) of a refill
+// takes the k-th ray not handed out yet, the rays ordered by (level, light, owner lane).
+//   LIST = false: a cursor (level cl, light cj, the group's unassigned owners cm) advanced by a scalar loop per
+//     refill, every lane finding its owner by a binary search over popcounts (kth_bit);
+//   LIST = true: that order written once per call into the wave's job list jl (LDS, rt_pool_list.hpp: 64 x LV x
+//     lights jobs of 2 bytes), so a refill is one rank (mbcnt), one LDS read and one scalar add. The launch takes this
+//     form where the list fits the kernel's LDS at 4 workgroups per CU (rt_hip.hip persist_kernel).
+// Both assign the same ray to the same lane in the same round, so every walk, wave step and counter is the same
+// (tests/test_pool_handout.py on the indexing, tests/test_gpu_pool_handout.py on the kernels).
+template <bool COUNT, int LV, bool TQ = false, bool LIST = false, class OKM>
 __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lvl, int* __restrict__ stk,
                                             int* __restrict__ sstk, int wcap, int regroup, Ctr& c, UCtr& u,
-                                            int* tq = nullptr) {
+                                            int* tq = nullptr, rtp::job_t* jl = nullptr) {
     const unsigned lane = threadIdx.x & 63u;
     // (TQ: the queue's result slots are clear, tq_clear)
     const unsigned long long all = uni64(__ballot(1));
@@ -123,62 +152,98 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
     int sp = 0;
     TopC tc;
     WNode N = {};
-    for (;;) {
-        advance();
-        const unsigned long long idle = uni64(__ballot(!busy));
-        if (idle == all && cm == 0) break;
-        if (cm != 0) {  // refill every idle lane while there is work
-            // every idle lane at once: the k-th requester takes the k-th unassigned owner of light cj, the rest
-            // move on to the next light (one round per light, no per-ray scalar loop)
-            unsigned long long req = idle;
-            bool got = false;
-            while (req != 0ull && cm != 0ull) {
-                const unsigned nreq = (unsigned)__builtin_popcountll(req), nav = (unsigned)__builtin_popcountll(cm);
-                const unsigned k = __builtin_amdgcn_mbcnt_hi((unsigned)(req >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((unsigned)req, 0u));
-                if (((req >> lane) & 1ull) && k < nav) {
-                    wo = kth_bit(cm, k) | (cl << 6) | (cj << 9);
-                    got = true;
-                }
-                if (nreq >= nav) {
-                    req = uni64(drop_low(req, nav));
-                    cm = 0ull;
-                    advance();
-                } else {
-                    cm = uni64(drop_low(cm, nreq));
-                    req = 0ull;
-                }
-            }
-            if (got) {
-                // the reference's shadow ray, light_v (raytracer.c:62-99) as path_step forms it, from the owner's hit
-                // point (its path-buffer slot)
-                const v3 ipo = xyz(lvl[wo & 511]);  // (64 level + owner)
-                const v3 Lp = xyz(s.lights[2 * (wo >> 9)]);
-                v3 l = sub(Lp, ipo);
-                const float mg = mag(l);
-                l = dvs(l, mg);
-                const v3 tmp = sub(ipo, Lp);
-                ld2 = dot(tmp, tmp);
-                o = ipo;
-                d = l;
-                if (degenerate(d) && !degenerate_ok(s, o, d)) {  // a 0 / 0 in the reference's slabs: walked strictly
-                    CTR_INC(c, fb, C_FALLBACK);
-                    if (visible_walk<true, COUNT, true>(s.ref, o, d, ld2, sstk ? sstk : stk, c))
-                        atomicOr(reinterpret_cast<unsigned*>(lvl + (wo & 511)) + 3, 1u << ((wo >> 9) & 31));
-                } else {
-                    reach = shadow_reach(o, ld2);
-                    p = ray_pre_shadow(o, d, reach);
-                    oct = (p.ix < 0.0f ? 1u : 0u) | (p.iy < 0.0f ? 2u : 0u) | (p.iz < 0.0f ? 4u : 0u);
-                    best = FMAX;
-                    sp = 0;
-                    N = wload_at(nbase, 0, c.top[1]);
-                    busy = true;
-                }
+    // LIST: the jobs in the cursor's order, `total` of them, `head` handed out
+    unsigned head = 0u, total = 0u;
+    if constexpr (LIST) {  // <budget:list build>
+        for (int l = 0; l < LV; ++l) {
+            const unsigned ok = okm(l);
+            if (uni64(__ballot(ok != 0u)) == 0ull) continue;  // (a level no path of the wave reached)
+            for (int j = 0; j < nl; ++j) {
+                const bool mine = ((ok >> j) & 1u) != 0u;
+                const unsigned long long M = uni64(__ballot(mine));
+                if (mine) jl[rtp::owner_slot(total, mbcnt64(M))] = rtp::job_of(lane, (unsigned)l, (unsigned)j);
+                total = rtp::next_base(total, M);
             }
         }
+        u.shad += total;
+        PRT_REFILL_CNT(c, q4, lane == 0u ? 1u : 0u);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // (the list is read by other lanes than wrote it)
+    }  // </budget>
+    for (;;) {
+        bool got = false;
+        if constexpr (LIST) {  // <budget:refill hand-out>
+            const unsigned long long idle = uni64(__ballot(!busy));
+            if (idle == all && head == total) break;
+            if (head < total) {  // refill every idle lane while there is work: the k-th idle lane takes job head + k
+                unsigned slot;
+                if (!busy && rtp::take(head, total, mbcnt64(idle), slot)) {
+                    wo = (int)jl[slot];
+                    got = true;
+                }
+                head = rtp::head_after(head, total, (unsigned)__builtin_popcountll(idle));
+                PRT_REFILL_CNT(c, q1, lane == 0u ? 1u : 0u);
+            }
+        } else {
+            advance();
+            const unsigned long long idle = uni64(__ballot(!busy));
+            if (idle == all && cm == 0) break;
+            if (cm != 0) {  // refill every idle lane while there is work
+                PRT_REFILL_CNT(c, q1, lane == 0u ? 1u : 0u);
+                // every idle lane at once: the k-th requester takes the k-th unassigned owner of light cj, the rest
+                // move on to the next light (one round per light, no per-ray scalar loop)
+                unsigned long long req = idle;
+                while (req != 0ull && cm != 0ull) {
+                    PRT_REFILL_CNT(c, q2, lane == 0u ? 1u : 0u);
+                    const unsigned nreq = (unsigned)__builtin_popcountll(req), nav = (unsigned)__builtin_popcountll(cm);
+                    const unsigned k = mbcnt64(req);
+                    if (((req >> lane) & 1ull) && k < nav) {
+                        wo = kth_bit(cm, k) | (cl << 6) | (cj << 9);
+                        got = true;
+                    }
+                    if (nreq >= nav) {
+                        req = uni64(drop_low(req, nav));
+                        cm = 0ull;
+                        advance();
+                    } else {
+                        cm = uni64(drop_low(cm, nreq));
+                        req = 0ull;
+                    }
+                }
+            }
+        }  // </budget>
+        if (got) {  // <budget:ray formation>
+            PRT_REFILL_CNT(c, q3, 1u);
+            // the reference's shadow ray, light_v (raytracer.c:62-99) as path_step forms it, from the owner's hit
+            // point (its path-buffer slot)
+            const v3 ipo = xyz(lvl[wo & 511]);  // (64 level + owner)
+            const v3 Lp = xyz(s.lights[2 * (wo >> 9)]);
+            v3 l = sub(Lp, ipo);
+            const float mg = mag(l);
+            l = dvs(l, mg);
+            const v3 tmp = sub(ipo, Lp);
+            ld2 = dot(tmp, tmp);
+            o = ipo;
+            d = l;
+            if (degenerate(d) && !degenerate_ok(s, o, d)) {  // a 0 / 0 in the reference's slabs: walked strictly
+                CTR_INC(c, fb, C_FALLBACK);
+                if (visible_walk<true, COUNT, true>(s.ref, o, d, ld2, sstk ? sstk : stk, c))
+                    atomicOr(reinterpret_cast<unsigned*>(lvl + (wo & 511)) + 3, 1u << ((wo >> 9) & 31));
+            } else {
+                // LIST: the reach from mg. sqrtf(ld2) is mg bit for bit: ipo - Lp is exactly -(Lp - ipo) component by
+                // component, a square loses the sign, and mag() and dot() add the three squares in the same order.
+                // (The cursor form, which k_shade's pool shares, keeps its expression; PRT_REACH_MAG=0: everywhere.)
+                reach = LIST && REACH_MAG ? shadow_reach_mag(o, mg) : shadow_reach(o, ld2);
+                p = ray_pre_shadow(o, d, reach);
+                oct = (p.ix < 0.0f ? 1u : 0u) | (p.iy < 0.0f ? 2u : 0u) | (p.iz < 0.0f ? 4u : 0u);
+                best = FMAX;
+                sp = 0;
+                N = wload_at(nbase, 0, c.top[1]);
+                busy = true;
+            }
+        }  // </budget>
         // walk until the wave is idle, or enough of it to refill while work is left: visible_wide's loop, one
         // ballot per step
-        const bool more = cm != 0 || cj + 1 < nl || cl + 1 < LV;
+        const bool more = LIST ? head < total : cm != 0 || cj + 1 < nl || cl + 1 < LV;
         for (;;) {
             unsigned th = 0u;
             int tb = 0, next = -1;
@@ -285,7 +350,8 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
 // level's colour and material afterwards. Across the pool a lane keeps only its direction, the hit triangle and the
 // lights' back-face mask; the hit point comes back from the slot, the normal and material from the shading record.
 // hpix >= 0: the pixel's output index, for hit / t (level 0) and bounce_hit.
-template <int MAXB, bool COUNT>
+// JL: the pool hands its rays out from the wave's job list (one level's: 64 x lights jobs, after the queues).
+template <int MAXB, bool COUNT, bool JL = false>
 __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v3 d, int* __restrict__ stk, Ctr& c,
                                              UCtr& u, int hpix, int* __restrict__ sstk, int wcap) {
     extern __shared__ int lds_dyn[];
@@ -296,6 +362,10 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
     int* tq = (int*)(pb0 + (size_t)BLOCK * MAXB) + (threadIdx.x >> 6) * TQ_WORDS;
     tq_clear(tq);
     const DScene& s = A.s;
+    rtp::job_t* jl = nullptr;
+    if constexpr (JL)
+        jl = (rtp::job_t*)((int*)(pb0 + (size_t)BLOCK * MAXB) + BLOCK / 64 * TQ_WORDS +
+                           uni((int)(threadIdx.x >> 6) * rtp::list_words(1, s.n_lights)));
     const v3 amb = mk(s.amb_x, s.amb_y, s.amb_z);
     int L = 0;
     bool tail = false;
@@ -343,8 +413,8 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
         if (nh) {
             u.skip += nh * (unsigned)s.n_lights;  // less the rays walked (shadow_pool counts those in u.shad)
             const unsigned sh0 = u.shad;
-            shadow_pool<COUNT, 1, true>(s, [&](int) { return okm; }, pbw + it * 64, stk, sstk, wcap, A.regroup, c, u,
-                                        tq);
+            shadow_pool<COUNT, 1, true, JL>(s, [&](int) { return okm; }, pbw + it * 64, stk, sstk, wcap, A.regroup, c,
+                                            u, tq, jl);
             u.skip -= u.shad - sh0;
         }
         if (hit >= 0) {  // raytracer.c:144-172 as path_step, the lights' visibility from the pool
@@ -412,15 +482,19 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
 // q.hid: this lane's level-0 slots; q.tq: the wave's queue when Q::TQ), its levels' closest hits
 // (q.closest_at(it, o, d, best, nd)) and what it keeps of them (q.out(it, orig, best)); A is then any struct with s,
 // bounces and regroup. The shading arithmetic exists once.
+// JL (frame kernels only): the pool hands its rays out from the wave's job list (64 x MAXB x lights jobs, after the
+// queues); k_shade's pool keeps the cursor.
 struct FramePath {
     static constexpr bool TQ = true;
 };
-template <int MAXB, bool COUNT, class ARGS = KArgs, class Q = FramePath>
+template <int MAXB, bool COUNT, class ARGS = KArgs, class Q = FramePath, bool JL = false>
 __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3 d, int* __restrict__ stk, Ctr& c,
                                              UCtr& u, int hpix, int* __restrict__ sstk, int wcap, const Q& q = Q()) {
     constexpr bool FRAME = std::is_same<Q, FramePath>::value;
+    static_assert(FRAME || !JL, "the job list lives in the frame kernels' LDS layout");
     float4 *pb, *pbw;
     int *hid, *tq;
+    rtp::job_t* jl = nullptr;
     if constexpr (FRAME) {
         extern __shared__ int lds_dyn[];
         float4* pb0 = (float4*)(lds_dyn + wstack_words(wcap, true) * BLOCK);
@@ -431,6 +505,9 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
         // the wave's packed-triangle queue (TQ_*): the closest walks' result slots empty, its counter 0
         tq = (int*)(pb0 + (size_t)BLOCK * MAXB) + BLOCK * MAXB + (threadIdx.x >> 6) * TQ_WORDS;
         tq_clear(tq);
+        if constexpr (JL)
+            jl = (rtp::job_t*)((int*)(pb0 + (size_t)BLOCK * MAXB) + BLOCK * MAXB + BLOCK / 64 * TQ_WORDS +
+                               uni((int)(threadIdx.x >> 6) * rtp::list_words(MAXB, A.s.n_lights)));
     } else {
         pb = q.pb;
         pbw = pb - (threadIdx.x & 63);
@@ -446,6 +523,8 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
     int L = 0;
     bool tail = false;
     unsigned nhits = 0;
+    // (the <budget:...> comments mark the parts tools/stream_budget.py prices)
+    // <budget:closest-level setup>
     for (int it = 0; it < A.bounces; ++it) {  // the closest hits of every level (raytracer.c:101-147, 163-172)
         const unsigned na = popc_wave(alive);
         if (na == 0) break;
@@ -510,15 +589,16 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
         const unsigned nh = popc_wave(hitl);
         u.hits += nh;
         nhits += nh;
-    }
+    }  // </budget>
     if (nhits) {  // every level's shadow rays as one pool
         u.skip += nhits * (unsigned)s.n_lights;
         const unsigned sh0 = u.shad;
-        shadow_pool<COUNT, MAXB, Q::TQ>(s, [&](int l) { return (unsigned)(okm >> (8 * l)) & 0xFFu; }, pbw, stk, sstk, wcap,
-                                        A.regroup, c, u, tq);
+        shadow_pool<COUNT, MAXB, Q::TQ, JL>(s, [&](int l) { return (unsigned)(okm >> (8 * l)) & 0xFFu; }, pbw, stk, sstk,
+                                            wcap, A.regroup, c, u, tq, jl);
         u.skip -= u.shad - sh0;
     }
     v3 dl = d0;  // level i's direction: the primary one, then each level's reflection
+    // <budget:shading>
     for (int it = 0; it < L; ++it) {  // the levels' colours (raytracer.c:144-160 as path_step), in order
         const int h = hid[it * 64];
         if (h < 0) {  // a miss (the path's last level): the background
@@ -557,19 +637,20 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
         pb[it * 64] = make_float4(col.x, col.y, col.z, __int_as_float(m));
         const v3 dd = mul(v, -1.0f);
         dl = normalize(add(dd, mul(n, 2.0f * __builtin_fabsf(dot(dd, n)))));
-    }
+    }  // </budget>
     return fold_pb<MAXB>(s, pb, L, tail);
 }
 
 // render_pixel (rt_kernels.hpp) for the shadow-pool kernels: called by EVERY lane of the wave (valid = the lane
 // holds a pixel of the frame), so that the path loop and the pool run in uniform control flow
-template <int MAXB, bool COUNT, bool SPP1, int SHP>
+template <int MAXB, bool COUNT, bool SPP1, int SHP, bool JL>
 __device__ __forceinline__ void render_pixel_shp(const KArgs& A, const Cam& C, int frame, int x, int k, bool valid,
                                                  int* __restrict__ stk, Ctr& c, UCtr& u, int* __restrict__ sstk,
                                                  int wcap) {
     auto trace = [&](v3 d, int hp) {
-        if constexpr (SHP == 2) return trace_path_dfr<MAXB, COUNT>(A, valid, C.pos, d, stk, c, u, hp, sstk, wcap);
-        else return trace_path_shp<MAXB, COUNT>(A, valid, C.pos, d, stk, c, u, hp, sstk, wcap);
+        if constexpr (SHP == 2)
+            return trace_path_dfr<MAXB, COUNT, KArgs, FramePath, JL>(A, valid, C.pos, d, stk, c, u, hp, sstk, wcap);
+        else return trace_path_shp<MAXB, COUNT, JL>(A, valid, C.pos, d, stk, c, u, hp, sstk, wcap);
     };
     const int y = image_row(A, k, frame);
     valid = valid && y < A.H;  // frame_shift: a rotated rank's compact rows past the image

@@ -93,7 +93,7 @@ class LaunchInfo(ctypes.Structure):  # rt_launch_info
 
 # rt_launch_info.build bits (RT_BUILD_*)
 BUILD_BITS = {"waves4": 1, "packed_stack": 2, "packed_tris": 4, "lds_paths": 8, "pool_level": 16, "pool_all": 32,
-              "trace": 64, "feedback": 128}
+              "trace": 64, "feedback": 128, "pool_list": 256}
 
 
 class CommInfo(ctypes.Structure):  # rt_comm_info

@@ -24,6 +24,7 @@ ACCEL_NAMES = {v: k for k, v in ACCEL.items()}
 FLAG_COUNTERS = 1
 FLAG_UNPACKED_STACK = 2  # the builds scenes of more than 2^24 wide nodes run (rt_hip.h RT_FLAG_UNPACKED_STACK)
 FLAG_UNPACKED_TRIS = 4   # the builds scenes of 2^26 or more triangles run (RT_FLAG_UNPACKED_TRIS)
+FLAG_POOL_CURSOR = 8     # the pool kernels' cursor hand-out, as where the job lists do not fit (RT_FLAG_POOL_CURSOR)
 QUERY_CHUNK = 256  # rays a wave of the query kernel takes at once (rt_query.hpp QUERY_CHUNK)
 
 
