@@ -724,7 +724,8 @@ int rt_download(rt_ctx* ctx, float* h_rgb, int* h_hit);
  * last render reported a traversal-stack overflow */
 int rt_sync(rt_ctx* ctx, float* kernel_ms);
 /* per-launch kernel times (HIP events recorded on the context stream around each kernel) of the last
- * n launches (n <= 64), oldest first; synchronises; returns the number written or < 0 */
+ * n launches (n <= 64), oldest first; synchronises; returns the number written or < 0. A launch's time is one value:
+ * rt_sync and rt_kernel_times read its event pair once and return that figure on every later call. */
 int rt_kernel_times(rt_ctx* ctx, float* ms, int n);
 /* Multi-GPU in one process without RCCL (the fallback of the CLI's --gpus N; also several contexts on ONE
  * device): gathers the last render of n contexts -- a frame or a frame batch, f32 rgb or BGRA8 (rt_outputs.bgra),

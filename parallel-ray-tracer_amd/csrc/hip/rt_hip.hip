@@ -175,6 +175,10 @@ struct rt_ctx {
     static constexpr int NEV = rtl::NEV;  // ring of per-launch event pairs (rt_kernel_times)
     hipEvent_t ev0s[NEV] = {}, ev1s[NEV] = {};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the last launch's pair
+    // a finished launch's time, read from its pair once and kept (launch_ms): ms_of[slot] is the time of launch
+    // ms_launch[slot] - 1 (0: none read yet)
+    float ms_of[NEV] = {};
+    long long ms_launch[NEV] = {};
     hipEvent_t gather_ev = nullptr;           // completion of the last rt_gather into this (root) context
     hipEvent_t copy_ev = nullptr;             // rt_gather: this (source) context's peer copies issued
     long long launches = 0;
@@ -3544,13 +3548,29 @@ int sync_checked(rt_ctx* ctx, const char* who) {
 }
 }  // namespace
 
+// The HIP-event time of render launch `launch` (one of the last NEV, finished). hipEventElapsedTime converts the pair's
+// device ticks with a clock calibration the runtime refreshes as it goes, so two reads of the same finished pair can
+// differ in the last digits (seen: 0.7003270 and 0.7003260 ms). rt_sync and rt_kernel_times report a launch's time as
+// one value: the first read is kept until the slot's pair is recorded again.
+static hipError_t launch_ms(rt_ctx* ctx, long long launch, float* ms) {
+    const int slot = (int)(launch % rt_ctx::NEV);
+    if (ctx->ms_launch[slot] != launch + 1) {
+        float t = 0.0f;
+        if (hipError_t e = hipEventElapsedTime(&t, ctx->ev0s[slot], ctx->ev1s[slot]); e != hipSuccess) return e;
+        ctx->ms_of[slot] = t;
+        ctx->ms_launch[slot] = launch + 1;
+    }
+    *ms = ctx->ms_of[slot];
+    return hipSuccess;
+}
+
 extern "C" int rt_sync(rt_ctx* ctx, float* kernel_ms) {
     if (!ctx) return RT_E_ARG;
     HIPC(hipSetDevice(ctx->device));
     if (int rc = sync_checked(ctx, "rt_sync")) return rc;
     if (kernel_ms) {
         *kernel_ms = 0.0f;
-        if (ctx->rendered) HIPC(hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+        if (ctx->rendered) HIPC(launch_ms(ctx, ctx->launches - 1, kernel_ms));
     }
     return RT_OK;
 }
@@ -3563,8 +3583,7 @@ extern "C" int rt_kernel_times(rt_ctx* ctx, float* ms, int n) {
     long long avail = ctx->launches < rt_ctx::NEV ? ctx->launches : rt_ctx::NEV;
     if (n > avail) n = (int)avail;
     for (int i = 0; i < n; i++) {  // oldest first among the last n launches
-        int slot = (int)((ctx->launches - n + i) % rt_ctx::NEV);
-        HIPC(hipEventElapsedTime(&ms[i], ctx->ev0s[slot], ctx->ev1s[slot]));
+        HIPC(launch_ms(ctx, ctx->launches - n + i, &ms[i]));
     }
     return n;
 }

@@ -671,6 +671,49 @@ __device__ __forceinline__ WNode wload_at(gnodes base, int node, const float4* t
     return WNode{f4(N[0]), f4(N[1]), f4(N[2]), f4(N[3]), f4(N[4])};
 }
 
+// PRT_PIN_ARGS: the walks' other kernel arguments held like the node array. Short of scalar registers, the compiler
+// re-read the stack's capacity (A.wcap: once per pop, twice per push, between the pop's two LDS reads) and the view's
+// triangle array (W.tris: in every iteration of every triangle loop, before the record's address) from the kernel
+// arguments, each an s_load with an s_waitcnt lgkmcnt(0) on the step's dependent chain. A value that has passed an
+// empty asm cannot be rematerialised from the kernarg segment: it stays in a scalar register or in a lane of a
+// spill register (a v_readlane, no wait).
+#ifndef PRT_PIN_ARGS
+#define PRT_PIN_ARGS 1
+#endif
+// PIN: the pool kernels (k_persist SHP 1 / 2) only. The kernels without a pool lost by it -- PERSIST4 on car_boxed
+// -1.3 %, on dragon871k -3.0 % -- so their walks read both as before.
+template <bool PIN = true>
+__device__ __forceinline__ int pin_s(int v) {
+    if (PRT_PIN_ARGS && PIN) __asm__ volatile("" : "+s"(v));
+    return v;
+}
+__device__ __forceinline__ gnodes tri_base(const float4* p) {
+    unsigned long long v = (unsigned long long)p;
+    if (PRT_PIN_ARGS) __asm__ volatile("" : "+s"(v));
+    return (gnodes)v;
+}
+// hit_triangle on the records at `tri` of a pinned triangle array
+template <bool FAST_RCP = false>
+__device__ __forceinline__ float hit_triangle_at(v3 o, v3 d, gnodes tri, int& nd) {
+    return hit_triangle_v<FAST_RCP>(o, d, f4(tri[0]), f4(tri[1]), f4(tri[2]), nd);
+}
+// a walk's triangle array: pinned (PIN), or the view's own field, read where it is used as before
+template <bool PIN>
+struct TriArr {
+    gnodes g;
+    const DWide* w;
+};
+template <bool PIN>
+__device__ __forceinline__ TriArr<PIN> tri_arr(const DWide& W) {
+    if constexpr (PIN) return TriArr<PIN>{tri_base(W.tris), nullptr};
+    else return TriArr<PIN>{nullptr, &W};
+}
+template <bool FAST_RCP, bool PIN>
+__device__ __forceinline__ float hit_tri(v3 o, v3 d, const TriArr<PIN>& T, int i, int& nd) {
+    if constexpr (PIN) return hit_triangle_at<FAST_RCP>(o, d, T.g + 3 * i, nd);
+    else return hit_triangle<FAST_RCP>(o, d, T.w->tris + 3 * i, nd);
+}
+
 
 // LATE (PRT_LATE_TRIS): th returns the hit leaf SLOTS (bits 0..7) and the walk forms the triangle bits from them with
 // leaf_tris after it has issued the next node's loads (the slot loop is off the dependent chain from this node's
@@ -949,8 +992,8 @@ constexpr unsigned TQ_MIN = PRT_TQ_MIN;
 // then applies the sequential loop's rule to the step's minimum m: m < best takes it (tie iff two pairs hit at m),
 // m == best (a hit) marks a tie -- the state the per-lane loop would leave, which is what the strict re-walk of a
 // tie relies on. Returns false when the step's pairs do not fit one round (the caller runs the loop).
-template <bool COUNT>
-__device__ __forceinline__ bool closest_tris_packed(const DWide& W, v3 o, v3 d, unsigned th, int tb, float& best,
+template <bool COUNT, bool PIN = false>
+__device__ __forceinline__ bool closest_tris_packed(const TriArr<PIN>& tris, v3 o, v3 d, unsigned th, int tb, float& best,
                                                     int& hp, int& nd, bool& tie, int* tq, Ctr& c) {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned long long ex = __builtin_amdgcn_read_exec();
@@ -979,7 +1022,7 @@ __device__ __forceinline__ bool closest_tris_packed(const DWide& W, v3 o, v3 d, 
     int k = 0;
     if (has) {
         PRT_TRI_ITER(c, q1);
-        tt = hit_triangle<true>(oo, dd, W.tris + 3 * (int)tri, k);
+        tt = hit_tri<true>(oo, dd, tris, (int)tri, k);
         if (COUNT) c.cht++;
         if (tt < FMAX) atomicMax(key + ow, ~(((unsigned long long)__float_as_uint(tt) << 32) | tri));
     }
@@ -1067,7 +1110,7 @@ __device__ __forceinline__ bool shadow_tris_packed(const DWide& W, v3 o, v3 d, f
 // PIPE: software-pipeline the leaf triangles (the next triangle's loads issued before this one's test);
 // pays where registers allow (the split kernels), not in k_persist (spills at its 168-VGPR cap).
 // TQ: a step whose lanes hold 3+ triangles tests them packed (closest_tris_packed; tq: the wave's queue).
-template <bool COUNT, bool PIPE = false, bool PK = false, bool TQ = false>
+template <bool COUNT, bool PIPE = false, bool PK = false, bool TQ = false, bool PIN = false>
 __device__ __forceinline__ void closest_wide(const DWide& W, v3 o, v3 d, float& best, int& hp, int& nd, bool& tie,
                                              int* __restrict__ stk, Ctr& c, int wcap = WSTACK, int* tq = nullptr,
                                              const float4* top = nullptr) {
@@ -1076,8 +1119,9 @@ __device__ __forceinline__ void closest_wide(const DWide& W, v3 o, v3 d, float& 
     int sp = 0;
     TopC tc;
     const gnodes nbase = walk_base(W.nodes);
+    const TriArr<PIN> tris = tri_arr<PIN>(W);
     WNode N = wload_at(nbase, 0, top);
-    for (;;) {
+    for (;;) {  // <step:closest> (tools/step_waits.py)
         unsigned nh, th, imask, nl;
         int cb, tb;
         pin_node(N);
@@ -1098,7 +1142,7 @@ __device__ __forceinline__ void closest_wide(const DWide& W, v3 o, v3 d, float& 
         }
         if constexpr (TQ) {
             if (__builtin_amdgcn_readfirstlane((int)(__ballot(__builtin_popcount(th) >= TQ_MIN) != 0ull)) &&
-                closest_tris_packed<COUNT>(W, o, d, th, tb, best, hp, nd, tie, tq, c))
+                closest_tris_packed<COUNT, PIN>(tris, o, d, th, tb, best, hp, nd, tie, tq, c))
                 th = 0u;
         }
         if (!PIPE) {
@@ -1107,7 +1151,7 @@ __device__ __forceinline__ void closest_wide(const DWide& W, v3 o, v3 d, float& 
                 const int i = tb + __builtin_ctz(th);
                 th &= th - 1u;
                 int k;
-                const float tt = hit_triangle<true>(o, d, W.tris + 3 * i, k);
+                const float tt = hit_tri<true>(o, d, tris, i, k);
                 if (COUNT) c.cht++;
                 if (tt < best) {
                     best = tt;
@@ -1156,7 +1200,7 @@ __device__ __forceinline__ void closest_wide(const DWide& W, v3 o, v3 d, float& 
             if (next == -2) CTR_INC(c, err, C_ERR);
             break;
         }
-    }
+    }  // </step>
 }
 
 template <bool COUNT, bool PIPE = false, bool PK = false, bool TQ = false>
@@ -1170,7 +1214,7 @@ __device__ __forceinline__ bool visible_wide(const DWide& W, v3 o, v3 d, float l
     TopC tc;
     const gnodes nbase = walk_base(W.nodes);
     WNode N = wload_at(nbase, 0, top);
-    for (;;) {
+    for (;;) {  // <step:shadow>
         unsigned nh, th, imask, nl;
         int cb, tb;
         pin_node(N);
@@ -1244,7 +1288,7 @@ __device__ __forceinline__ bool visible_wide(const DWide& W, v3 o, v3 d, float l
             if (next == -2) CTR_INC(c, err, C_ERR);
             break;
         }
-    }
+    }  // </step>
     return true;
 }
 
@@ -1280,7 +1324,7 @@ __device__ __forceinline__ float tie_bound(v3 o, float tmin) {
 // Closest hit with the kernel's policy; returns the ORIGINAL triangle index (-1 = miss).
 // sstk (nullable): the binary walks' stack when the wide walk's `stk` holds only wcap entries (DYN kernels)
 // unit: d has unit length (a reflection ray): the unit-direction view serves the fast walk
-template <bool STRICT, bool COUNT, bool REG = true, bool PIPE = false, bool PK = false, bool TQ = false>
+template <bool STRICT, bool COUNT, bool REG = true, bool PIPE = false, bool PK = false, bool TQ = false, bool PIN = false>
 __device__ __forceinline__ int closest(const DScene& s, v3 o, v3 d, float& best, int& nd, int* __restrict__ stk,
                                        Ctr& c, int* __restrict__ sstk = nullptr, int wcap = WSTACK, bool unit = false,
                                        int* tq = nullptr) {
@@ -1297,7 +1341,7 @@ __device__ __forceinline__ int closest(const DScene& s, v3 o, v3 d, float& best,
         int orig = -1;
         if (s.wide.nodes) {
             const DWide& W = wide_for(s, unit);
-            closest_wide<COUNT, PIPE, PK, TQ>(W, o, d, best, hp, nd, tie, stk, c, wcap, tq, c.top[unit ? 1 : 0]);
+            closest_wide<COUNT, PIPE, PK, TQ, PIN>(W, o, d, best, hp, nd, tie, stk, c, wcap, tq, c.top[unit ? 1 : 0]);
             if (!tie) {
                 orig = hp >= 0 ? W.tri_orig[hp] : -1;
                 done = true;
@@ -1835,7 +1879,7 @@ void k_persist(KArgs A) {
         extern __shared__ int lds_dyn[];
         stk = lds_dyn + threadIdx.x;
         sstk = A.gstack + (size_t)blockIdx.x * STACK * BLOCK + threadIdx.x;
-        wcap = A.wcap;
+        wcap = pin_s<SHP == 1 || SHP == 2>(A.wcap);  // (PRT_PIN_ARGS)
     } else {
         __shared__ int lds[STACK * BLOCK];
         stk = lds + threadIdx.x;

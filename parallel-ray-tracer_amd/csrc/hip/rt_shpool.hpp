@@ -100,6 +100,43 @@ __device__ __forceinline__ void flush_u(const UCtr& u, unsigned long long* g) {
 // owner's ray fetched by `ds_bpermute`; occlusion (the reference's per-triangle test, bvh.c:283-290) and the nearest
 // hit (for the walk's box pruning) go back to the owner's LDS slots.
 
+// The pool step's waits. The step issues the next node's five loads before its triangle tests so that
+// one memory latency covers both; two things in the compiled step undid that, and each has a switch here.
+// PRT_STEP_OWN_LEAF: the node's leaf words (f1.z, f1.w) and its triangle base (f1.y) are read by leaf_tris and the
+// triangle tests AFTER the next node's loads are issued, so they kept the pinned f1 quad alive, the new f1 landed in a temporary quad, and its copy into the pinned quad -- with
+// the s_waitcnt vmcnt it needs -- sat at the end of the `if (busy)` block, before any triangle load. With the three words
+// moved to registers of their own first, the new quad lands where the node test reads it and nothing waits.
+#ifndef PRT_STEP_OWN_LEAF
+#define PRT_STEP_OWN_LEAF 1
+#endif
+__device__ __forceinline__ void own_leaf_words(unsigned& m0, unsigned& m1, int& tb) {
+    if (PRT_STEP_OWN_LEAF) {  // (real moves into early-clobber outputs: a "+v" operand is coalesced with the quad's register)
+        unsigned a, b;
+        int t;
+        __asm__ volatile("v_mov_b32 %0, %3\n\tv_mov_b32 %1, %4\n\tv_mov_b32 %2, %5"
+                         : "=&v"(a), "=&v"(b), "=&v"(t)
+                         : "v"(m0), "v"(m1), "v"(tb));
+        m0 = a;
+        m1 = b;
+        tb = t;
+    }
+}
+// PRT_TRI_LANDED: hit_triangle's |det| early-out skips the use of two of a record's three quads, so their loads could
+// be pending at the triangle loop's back edge, and since the next iteration writes the registers they land in, the
+// compiler drained every load (the next node's included) with s_waitcnt vmcnt(0) at the loop's top. tri_landed names
+// the three quads as inputs of an empty asm after the test: every path through an iteration has then waited for its own
+// record (a counted wait the in-order counter has mostly satisfied already) and the loop's top needs none.
+#ifndef PRT_TRI_LANDED
+#define PRT_TRI_LANDED 1
+#endif
+struct TriRec {
+    pin4 a, b, c;
+};
+__device__ __forceinline__ TriRec tri_load(gnodes t) { return TriRec{t[0], t[1], t[2]}; }
+__device__ __forceinline__ void tri_landed(const TriRec& R) {
+    if (PRT_TRI_LANDED) __asm__ volatile("" ::"v"(R.a), "v"(R.b), "v"(R.c));
+}
+
 // The shadow rays of LV bounce levels of the wave's paths, walked as ONE wave-level pool.
 // okm(l): bit j = this lane's path hit a surface at level l and light j passed the back-face test (dot(L - ip, n)
 // >= 0, the reference's early-out, raytracer.c:66-67; failing lights are not walked). lvl: the wave's path-buffer
@@ -127,6 +164,7 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
     const int nl = s.n_lights;
     const DWide& W = wide_for(s, true);  // |d| = 1: the unit-direction view
     const gnodes nbase = walk_base(W.nodes);
+    const gnodes tris = tri_base(W.tris);
     // the cursor (wave-uniform): level cl, light cj, and the owner lanes whose ray toward it is still unassigned
     int cl = 0, cj = -1;
     unsigned long long cm = 0;
@@ -244,7 +282,7 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
         // walk until the wave is idle, or enough of it to refill while work is left: visible_wide's loop, one
         // ballot per step
         const bool more = LIST ? head < total : cm != 0 || cj + 1 < nl || cl + 1 < LV;
-        for (;;) {
+        for (;;) {  // <step:pool> (the marks: tools/step_waits.py lists this loop's loads and waits)
             unsigned th = 0u;
             int tb = 0, next = -1;
             if (busy) {  // one step of visible_wide
@@ -253,7 +291,8 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
                 pin_node(N);
                 wide_node<COUNT, LATE_TRIS, SHADOW_CLAMP ? 1 : 0>(N, p, oct, fminf(best * PRUNE_SLACK, reach), nh, th, cb, tb,
                                                           imask, nlf, SHADOW_ORDER_XOR);
-                const unsigned m0 = __float_as_uint(N.f1.z), m1 = __float_as_uint(N.f1.w);
+                unsigned m0 = __float_as_uint(N.f1.z), m1 = __float_as_uint(N.f1.w);
+                own_leaf_words(m0, m1, tb);
                 next = wide_step_next<true>(nh, cb, imask, oct ^ SHADOW_ORDER_XOR, sp, tc, stk, wcap);
                 N = wload_at(nbase, next >= 0 ? next : 0, c.top[1]);  // unconditional (closest_wide)
                 top_reload<true>(sp, tc, stk, wcap);
@@ -288,7 +327,9 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
                             if (j < T) {
                                 PRT_TRI_ITER(c, q2);
                                 int k;
-                                const float tt = hit_triangle<SHADOW_RCP>(oo, dd, W.tris + 3 * (int)(job & 0x3FFFFFFu), k);
+                                const TriRec R = tri_load(tris + 3 * (int)(job & 0x3FFFFFFu));
+                                const float tt = hit_triangle_v<SHADOW_RCP>(oo, dd, f4(R.a), f4(R.b), f4(R.c), k);
+                                tri_landed(R);
                                 if (COUNT) c.sht++;
                                 if (tt < FMAX) {
                                     const v3 q = add(oo, mul(dd, tt));
@@ -316,7 +357,9 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
                     const int i = tb + __builtin_ctz(th);
                     th &= th - 1u;
                     int k;
-                    const float tt = hit_triangle<SHADOW_RCP>(o, d, W.tris + 3 * i, k);
+                    const TriRec R = tri_load(tris + 3 * i);
+                    const float tt = hit_triangle_v<SHADOW_RCP>(o, d, f4(R.a), f4(R.b), f4(R.c), k);
+                    tri_landed(R);
                     if (COUNT) c.sht++;
                     if (tt < best) {
                         best = tt;
@@ -337,7 +380,7 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
             }
             const unsigned long long id2 = uni64(__ballot(!busy));
             if (id2 == all || (more && __builtin_popcountll(id2) >= regroup)) break;
-        }
+        }  // </step>
     }
     if constexpr (TQ) tq_clear(tq);  // (the pool's jobs 64..127 overwrote the closest walk's flag words)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -381,7 +424,7 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
         if (alive) {  // raytracer.c:101-147 as path_step
             float best;
             int nd;
-            const int orig = closest<false, COUNT, true, false, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
+            const int orig = closest<false, COUNT, true, false, true, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
             if (hpix >= 0) {
                 const int h = opaque(hpix);  // (the outputs' addresses formed here, not hoisted and held: OPAQUE_OUT)
                 if (it == 0) {
@@ -537,7 +580,7 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
             int nd;
             int orig;
             if constexpr (FRAME) {
-                orig = closest<false, COUNT, true, false, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
+                orig = closest<false, COUNT, true, false, true, true, true>(s, o, d, best, nd, stk, c, sstk, wcap, it > 0, tq);
                 if (hpix >= 0) {
                     const int h = opaque(hpix);  // (the outputs' addresses formed here, not hoisted and held: OPAQUE_OUT)
                     if (it == 0) {

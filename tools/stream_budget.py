@@ -36,19 +36,21 @@ HIP = os.path.join(ROOT, "parallel-ray-tracer_amd", "csrc", "hip")
 # function -> part (rt_kernels.hpp, rt_shpool.hpp); what is not named lands in "other" and is listed
 PARTS = {
     "node test": ["wide_node", "pin_q", "pin_node", "wload", "wload_at", "f4", "plane_pair", "plane_sel", "shift_in",
-                  "far_sel", "max_raw", "min_raw", "max3_raw", "min3_raw", "fma_half", "fma_half_clamp", "closest_lim"],
-    "triangle tests": ["hit_triangle", "leaf_tris", "closest_tris_packed", "shadow_tris_packed", "tq_clear"],
+                  "far_sel", "max_raw", "min_raw", "max3_raw", "min3_raw", "fma_half", "fma_half_clamp", "closest_lim",
+                  "own_leaf_words"],
+    "triangle tests": ["hit_triangle", "hit_triangle_at", "hit_tri", "tri_load", "tri_landed", "leaf_tris", "closest_tris_packed",
+                       "shadow_tris_packed", "tq_clear"],
     "stack": ["wide_next", "wide_next_tc", "top_reload", "wide_step_next"],
     "walk loop": ["closest_wide", "visible_wide", "count_step", "first_active_lane"],
     "ray formation": ["ray_pre_shadow", "shadow_reach", "shadow_reach_mag", "degenerate", "degenerate_ok", "on_face"],
     "refill hand-out": ["kth_bit", "drop_low", "mbcnt64"],
     "closest-level setup": ["closest", "ray_pre_closest", "tie_bound", "wide_for", "walk_base", "primary_dir",
                             "primary_dir_sample", "cam_of", "image_row", "opaque", "popc_wave", "trace_path_dfr",
-                            "trace_path_shp"],
+                            "trace_path_shp", "tri_base", "tri_arr"],
     "shading": ["fold_pb"],
     "strict fallback": ["closest_walk", "visible_walk", "children", "children_out", "visit", "ref_reaches"],
     "tile loop": ["k_persist", "next_item", "lane_now", "lane_slot", "render_pixel_shp", "store_px", "clamp01", "flush",
-                  "flush_u", "wave_sum", "ev_add", "ev_lds", "uni", "uni64"],
+                  "flush_u", "wave_sum", "ev_add", "ev_lds", "uni", "uni64", "pin_s"],
 }
 FUNC_PART = {f: p for p, fs in PARTS.items() for f in fs}
 FUNC_PART["shadow_pool"] = "walk loop"  # (its lines outside the budget marks: the pool's walk loop)
