@@ -608,6 +608,88 @@ typedef struct rt_overlaps_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info);
 
+/* Sweep queries: per caller-supplied moving sphere the first contact with the mesh -- the query for a body of finite
+ * size that moves (continuous collision of particles, camera and character probes, thick rays, path clearance): raycast,
+ * overlap, sweep.
+ * Query i is a sphere of radius r whose centre at time t is c + t d, d not normalised, over 0 <= t <= T with
+ * T = fminf(t_max[i], FLT_MAX) (t_max NULL or +inf: no bound). Its answer is the first element of
+ *   S_i = { j : toi(i, triangle j) exists }, ordered by (toi ascending, original index ascending):
+ * a total order, so the answer depends on no BVH, and triangles that share the touched edge or vertex (an exact tie)
+ * answer with the lowest index. S_i is empty, decided before any walk, when any of c, d, r is non-finite, when r < 0,
+ * and when t_max[i] is NaN or negative. 0 is a valid bound ("does it touch now"), d = 0 a valid motion with the same
+ * meaning, r = 0 a valid thin sweep. No input value is an error.
+ * toi is computed in float32 exactly as follows on a triangle's record a = v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0), every
+ * operation rounded to float32, dot(u, v) = u.x*v.x + u.y*v.y + u.z*v.z left to right, no FMA, IEEE division and sqrtf,
+ * fminf / fmaxf with C semantics. With b = a + e1, cc = a + e2, r2 = r*r, dd = dot(d, d):
+ *   1. The gate. tlo = fminf(fminf(a, b), cc); thi = fmaxf(fmaxf(a, b), cc)   (rt_overlap_boxes' step 1)
+ *      glo = tlo - r; ghi = thi + r; t0 = 0; t1 = T; then for each axis k:
+ *        d.k == 0: the triangle is out unless glo.k <= c.k && c.k <= ghi.k
+ *        else      inv = 1 / d.k; ta = (glo.k - c.k) * inv; tb = (ghi.k - c.k) * inv
+ *                  t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb))
+ *      the triangle is out unless t0 <= t1
+ *   2. Recentre. c0 = c + d*t0. If D(c0, triangle) <= r2 (rt_nearest_points' D) then toi = t0; with t0 = 0 this is a
+ *      sphere that touches at the start.
+ *   3. Candidates u >= 0 measured from t0; the least valid one counts.
+ *      face:     n = rt_overlap_boxes' nrm; nn = dot(n, n); ln = sqrtf(nn); so = dot(n, c - a); dn = dot(n, d)
+ *                sg = so < 0 ? -1 : 1; tf = (sg*(r*ln) - so) / dn
+ *                valid when nn > 0 && dn*sg < 0 && tf >= 0 and rt_nearest_points' region algorithm at c + d*tf reaches
+ *                its last case (the interior); u = fmaxf(tf - t0, 0). (The face uses the ORIGINAL centre: the plane's
+ *                side is not decided at c0, which lies within rounding of a flat triangle's plane when r is small.)
+ *      edges (p, f) = (a, e1), (a, e2), (b, e2 - e1):
+ *                m = c0 - p; md = dot(m, f); nd = dot(d, f); ff = dot(f, f); A = ff*dd - nd*nd; K = dot(m, m) - r2
+ *                Cq = ff*K - md*md; Bq = ff*dot(m, d) - nd*md; disc = Bq*Bq - A*Cq; u = (-Bq - sqrtf(disc)) / A
+ *                s = md + u*nd; valid when A > 0 && disc >= 0 && u >= 0 && 0 <= s && s <= ff
+ *      vertices v = a, b, cc:
+ *                m = c0 - v; Bv = dot(m, d); Cv = dot(m, m) - r2; disc = Bv*Bv - dd*Cv; u = (-Bv - sqrtf(disc)) / dd
+ *                valid when dd > 0 && disc >= 0 && u >= 0
+ *      No valid candidate: the triangle is out. Otherwise toi = t0 + u, and the triangle is in S_i iff toi <= T.
+ * This is the ray c + t d against the Minkowski sum of the triangle and the sphere: the prism's side walls lie inside the
+ * edge cylinders and the cylinders' caps inside the vertex spheres, so the least valid candidate is the first entry.
+ * The set differs from the real-number one only within rounding of a grazing contact. toi >= t0 holds by construction,
+ * and the gate is monotone in the box planes: the walk drops a subtree whose gate interval is empty or starts strictly
+ * after the best toi so far, with no margin. r = 0 is a thin sweep whose bits are NOT rt_trace_hits': it
+ * is another formula, with none of the ray tests' EPSILON culls.
+ * Results: tri[i] = the original triangle index, t[i] = toi, point[i] = rt_nearest_points' P of the centre
+ * C = c + d*toi on that triangle: the contact point (the caller's normal is C - P). The empty set gives -1, FLT_MAX and
+ * c's own bits.
+ * RT_KERNEL_STRICT runs every sweep against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * slots in order of their gate t0 and pruned by the best toi, and answers with the same bits. A scene without a wide view
+ * (RT_ACCEL_REFERENCE) runs the exhaustive loop under either kernel, and so does, under RT_KERNEL_FAST, a sweep outside
+ * the walk's domain: max|c.k| <= 2^20 mx, r <= 2^20 mx (mx: rt_update_info.scene_magnitude's quantity) and every nonzero
+ * |d.k| within [2^-64, 2^64], where the gate makes no NaN.
+ * A sweep query touches nothing a render or any other query owns. */
+typedef struct rt_spheres {
+    const float* centre;  /* device, [n][3] f32: c */
+    const float* motion;  /* device, [n][3] f32: d, not normalised; the centre at time t is c + t d */
+    const float* radius;  /* device, [n] f32: r >= 0 */
+    const float* t_max;   /* device, [n] f32, nullable (NULL or +inf: no bound) */
+    int n;                /* >= 0; 0 is RT_OK and launches nothing */
+    int kernel;           /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_spheres;
+typedef struct rt_sweep_results {   /* device pointers, all nullable, at least one non-null when n > 0 */
+    int* tri;     /* [n] */
+    float* t;     /* [n] */
+    float* point; /* [n][3] */
+} rt_sweep_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, a null centre, motion or radius with n > 0, all three outputs NULL with n > 0, an unknown
+ * kernel, a negative n. */
+int rt_sweep_spheres(rt_ctx* ctx, const rt_spheres* spheres, const rt_sweep_results* out);
+typedef struct rt_sweep_info {
+    long long spheres, found;     /* found: sweeps with a non-empty S_i */
+    long long empty_spheres;      /* spheres - found */
+    long long walked_spheres;     /* sweeps that walked the wide view */
+    long long exhaustive_spheres; /* sweeps run against every triangle: all valid ones under RT_KERNEL_STRICT or without
+                                     a wide view, and those outside the walk's domain (an invalid sweep is in neither) */
+    long long nodes_visited;      /* wide nodes decoded, summed over the sweeps (a level popped again counts again) */
+    long long tris_tested;        /* evaluations of toi, summed over the sweeps (exhaustive: sweeps x triangles) */
+    long long stack_overflows;    /* must be 0 */
+    float kernel_ms;              /* HIP events around the query's launch */
+} rt_sweep_info;
+/* counters of the last sweep query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are not
+ * valid), RT_E_STATE before the first */
+int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

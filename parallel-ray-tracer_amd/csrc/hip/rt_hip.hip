@@ -39,6 +39,7 @@
 #include "rt_nearest.hpp"
 #include "rt_neighbours.hpp"
 #include "rt_overlap.hpp"
+#include "rt_sweep.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -262,6 +263,11 @@ struct rt_ctx {
     hipEvent_t o_ev0 = nullptr, o_ev1 = nullptr;
     bool overlaps_run = false, o_launched = false;
     std::unordered_map<const void*, int> o_resident;  // resident workgroups of each k_overlap instantiation
+    // sweep queries (rt_sweep_spheres, rt_sweep.hpp): their own again ([rtd::SW_NCOUNT] counters, then the chunk counter)
+    unsigned long long* d_swq = nullptr;
+    hipEvent_t w_ev0 = nullptr, w_ev1 = nullptr;
+    bool sweeps_run = false, w_launched = false;
+    std::unordered_map<const void*, int> w_resident;  // resident workgroups of each k_sweep instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3526,6 +3532,85 @@ extern "C" int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- sweep queries (rt_sweep.hpp)
+extern "C" int rt_sweep_spheres(rt_ctx* ctx, const rt_spheres* r, const rt_sweep_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_sweep_spheres: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_sweep_spheres: null spheres / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_sweep_spheres: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_sweep_spheres: negative sphere count");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->centre || !r->motion || !r->radius))
+        return arg_err(ctx, "rt_sweep_spheres: null centre / motion / radius");
+    if (r->n > 0 && !out->tri && !out->t && !out->point)
+        return arg_err(ctx, "rt_sweep_spheres: needs a tri, a t or a point output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::SW_NCOUNT + 1);
+    if (!ctx->d_swq) HIPC(hipMalloc((void**)&ctx->d_swq, cbytes));
+    if (!ctx->w_ev0) HIPC(hipEventCreate(&ctx->w_ev0));
+    if (!ctx->w_ev1) HIPC(hipEventCreate(&ctx->w_ev1));
+    HIPC(hipMemsetAsync(ctx->d_swq, 0, cbytes, ctx->stream));
+    ctx->sweeps_run = true;
+    ctx->w_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::SWArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.centre = r->centre;
+    A.motion = r->motion;
+    A.radius = r->radius;
+    A.t_max = r->t_max;
+    A.tri = out->tri;
+    A.t = out->t;
+    A.out = out->point;
+    A.counters = ctx->d_swq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_swq + rtd::SW_NCOUNT);
+    A.n = r->n;
+    A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::sweep_domain
+    void (*k)(rtd::SWArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_sweep<true> : rtd::k_sweep<false>;
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->w_resident.find((const void*)k);
+    if (res == ctx->w_resident.end()) res = ctx->w_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->w_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->w_ev1, ctx->stream));
+    ctx->w_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->sweeps_run) {
+        ctx->err = "rt_get_sweep_info: no sweep query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::SW_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_swq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->spheres = (long long)c[rtd::SW_SPHERES];
+    info->found = (long long)c[rtd::SW_FOUND];
+    info->empty_spheres = (long long)c[rtd::SW_EMPTY];
+    info->walked_spheres = (long long)c[rtd::SW_WALKED];
+    info->exhaustive_spheres = (long long)c[rtd::SW_EXH];
+    info->nodes_visited = (long long)c[rtd::SW_NODES];
+    info->tris_tested = (long long)c[rtd::SW_TRIS];
+    info->stack_overflows = (long long)c[rtd::SW_ERR];
+    if (ctx->w_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->w_ev0, ctx->w_ev1));
+    if (c[rtd::SW_ERR]) {
+        ctx->err = "rt_get_sweep_info: the query's traversal stack overflowed " + std::to_string(c[rtd::SW_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4406,6 +4491,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_ovq) (void)hipFree(ctx->d_ovq);
     if (ctx->o_ev0) (void)hipEventDestroy(ctx->o_ev0);
     if (ctx->o_ev1) (void)hipEventDestroy(ctx->o_ev1);
+    if (ctx->d_swq) (void)hipFree(ctx->d_swq);
+    if (ctx->w_ev0) (void)hipEventDestroy(ctx->w_ev0);
+    if (ctx->w_ev1) (void)hipEventDestroy(ctx->w_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

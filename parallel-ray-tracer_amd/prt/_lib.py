@@ -214,6 +214,22 @@ class OverlapsInfo(ctypes.Structure):  # rt_overlaps_info
                 ("kernel_ms", ctypes.c_float)]
 
 
+class Spheres(ctypes.Structure):  # rt_spheres
+    _fields_ = [("centre", ctypes.c_void_p), ("motion", ctypes.c_void_p), ("radius", ctypes.c_void_p),
+                ("t_max", ctypes.c_void_p), ("n", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class SweepResults(ctypes.Structure):  # rt_sweep_results
+    _fields_ = [("tri", ctypes.c_void_p), ("t", ctypes.c_void_p), ("point", ctypes.c_void_p)]
+
+
+class SweepInfo(ctypes.Structure):  # rt_sweep_info
+    _fields_ = [("spheres", ctypes.c_longlong), ("found", ctypes.c_longlong), ("empty_spheres", ctypes.c_longlong),
+                ("walked_spheres", ctypes.c_longlong), ("exhaustive_spheres", ctypes.c_longlong),
+                ("nodes_visited", ctypes.c_longlong), ("tris_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -341,6 +357,8 @@ def hip():
         L.rt_get_neighbours_info.argtypes = [ctypes.c_void_p, P(NeighboursInfo)]
         L.rt_overlap_boxes.argtypes = [ctypes.c_void_p, P(Boxes), P(OverlapResults)]
         L.rt_get_overlaps_info.argtypes = [ctypes.c_void_p, P(OverlapsInfo)]
+        L.rt_sweep_spheres.argtypes = [ctypes.c_void_p, P(Spheres), P(SweepResults)]
+        L.rt_get_sweep_info.argtypes = [ctypes.c_void_p, P(SweepInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

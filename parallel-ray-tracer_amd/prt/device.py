@@ -662,6 +662,81 @@ class Renderer:
         self._chk(_L.rt_get_overlaps_info(self._ctx, ctypes.byref(i)), "rt_get_overlaps_info")
         return {f: getattr(i, f) for f, _ in _lib.OverlapsInfo._fields_}
 
+    def sweep(self, centres, motions, radius, t_max=None, kernel="fast", tri=None, t=None, point=None):
+        """rt_sweep_spheres: per moving sphere -- centre c + t d at time t, radius r -- its first contact with the scene:
+        the first triangle by (toi, original triangle index), whatever the BVH (include/rt_hip.h states toi) -> (tri [n]
+        int32, -1 when nothing is touched within the bound; t [n] float32 = toi, FLT_MAX then; point [n, 3] float32 =
+        the contact point, the centre's own bits then). The caller's normal is (c + t d) - point. centres, motions:
+        [n, 3] float32 contiguous tensors on this device (or raw pointers: centres=(pointer, n), motions=pointer, with
+        radius a raw pointer too); motions are not normalised, and d = 0 asks "does it touch now". radius: a float, or
+        an [n] float32 tensor (r >= 0; 0 is a thin sweep). t_max: optional [n] float32 tensor of bounds on t (+inf: none;
+        0: touching now; NaN or negative: nothing). kernel="strict" runs every sweep against every triangle (the
+        checker), "fast" / "auto" walks the full wide view with the same bits. tri / t / point: optional outputs
+        (allocated when not given). Asynchronous on the renderer's stream: sync() or sweep_info() before the results
+        are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if isinstance(centres, tuple):
+            pc, n = centres
+            if (not isinstance(pc, int) or not isinstance(n, int) or n < 0 or not isinstance(motions, int) or
+                    isinstance(radius, bool) or not isinstance(radius, int)):
+                raise RtError("spheres: raw pointers are given as centres=(pointer, n), motions=pointer, radius=pointer")
+            pd, pr = motions, radius
+        else:
+            for x, what in ((centres, "centres"), (motions, "motions")):
+                if not isinstance(x, torch.Tensor):
+                    raise RtError(f"{what}: expected a torch tensor or raw pointers, got {type(x).__name__}")
+                if x.dim() != 2 or x.shape[1] != 3:
+                    raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, 3]")
+            n = centres.shape[0]
+            if motions.shape[0] != n:
+                raise RtError(f"motions: {motions.shape[0]} spheres, centres has {n}")
+            if isinstance(radius, torch.Tensor):
+                if radius.dim() != 1:
+                    raise RtError(f"radius: shape {tuple(radius.shape)}, expected [n]")
+                if radius.shape[0] != n:
+                    raise RtError(f"radius: {radius.shape[0]} spheres, centres has {n}")
+            elif isinstance(radius, bool) or not isinstance(radius, (int, float)):
+                raise RtError(f"radius: expected a float or a torch tensor, got {type(radius).__name__}")
+        if t_max is not None and not isinstance(t_max, (torch.Tensor, int)):
+            raise RtError(f"t_max: expected a torch tensor, got {type(t_max).__name__}")
+        if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
+            raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
+        if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
+        if not isinstance(centres, tuple):
+            pc = _ptr(centres, "centres", 3 * n, f32, self.device)
+            pd = _ptr(motions, "motions", 3 * n, f32, self.device)
+        pm = _ptr(t_max, "t_max", n, f32, self.device)
+        for x, what, k, dt in ((tri, "tri", n, i32), (t, "t", n, f32), (point, "point", 3 * n, f32)):
+            _ptr(x, what, k, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if not isinstance(centres, tuple):
+            if not isinstance(radius, torch.Tensor):
+                radius = torch.full((n,), float(radius), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(self.device).synchronize()  # (the fill is torch's work, the query runs on ours)
+            pr = _ptr(radius, "radius", n, f32, self.device)
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+        if point is None:
+            point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        res = _lib.SweepResults(_ptr(tri, "tri", n, i32, self.device), _ptr(t, "t", n, f32, self.device),
+                                _ptr(point, "point", 3 * n, f32, self.device))
+        q = _lib.Spheres(pc, pd, pr, pm, n, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_sweep_spheres(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_sweep_spheres")
+        self._sweep_keep = radius  # (a radius tensor made here lives until the next sweep: the launch is asynchronous)
+        return tri, t, point
+
+    def sweep_info(self):
+        """rt_get_sweep_info: the last sweep query's counters (spheres, found, empty_spheres, walked_spheres,
+        exhaustive_spheres, nodes_visited, tris_tested) and kernel_ms; synchronises; raises when the query overflowed
+        its stack"""
+        i = _lib.SweepInfo()
+        self._chk(_L.rt_get_sweep_info(self._ctx, ctypes.byref(i)), "rt_get_sweep_info")
+        return {f: getattr(i, f) for f, _ in _lib.SweepInfo._fields_}
+
     def overlaps_csr(self, lo, hi, kernel="auto"):
         """every box's full S_i, in index order -> (offsets [n + 1] int32, tris [offsets[n]] int32): box i's triangles
         are tris[offsets[i]:offsets[i + 1]], ascending. Two launches of rt_overlap_boxes -- a pure count, then the list

@@ -14,13 +14,15 @@ The fast and the strict kernel answer with the same bits (checked here on every 
 --mode shade times rt_shade_rays instead (shade_mode below), --mode hits rt_trace_hits beside the
 closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below),
 --mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below), --mode overlap
-rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below).
+rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below), --mode sweep
+rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
        python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]
        python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -37,14 +39,16 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap"],
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
                          "nearest: rt_nearest_points beside the closest-hit query (nearest_mode); "
                          "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode); "
-                         "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode)")
-    ap.add_argument("--out", default=None, help="nearest, neighbours, overlap: also append the raw lines to this file")
+                         "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode); "
+                         "sweep: rt_sweep_spheres beside the closest-hit query (sweep_mode)")
+    ap.add_argument("--out", default=None,
+                    help="nearest, neighbours, overlap, sweep: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -62,6 +66,8 @@ def main():
         return neighbours_mode(a, md5)
     if a.mode == "overlap":
         return overlap_mode(a, md5)
+    if a.mode == "sweep":
+        return sweep_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -560,6 +566,87 @@ def overlap_mode(a, md5):
             if total > CSR_CAP:
                 print(json.dumps({"scene": name, "set": label, "arm": "csr", "skipped": "set_entries above the cap",
                                   "set_entries": total, "cap": CSR_CAP}), flush=True)
+        r.close()
+    if out:
+        out.close()
+
+
+def sweep_mode(a, md5):
+    """--mode sweep: per scene, rt_sweep_spheres on W x H sweeps (1920 x 1080 by default) whose (c, d)
+    are the camera's primary rays, and the unit-length bounce rays of the trace mode (from the primary hit points in
+    random directions: with r > 0 most of these touch at the start), with radii of 0, 0.1 %, 1 % and 5 % of the scene's
+    extent (its box's longest side), beside rt_trace_rays' closest hit on the same rays, and the exhaustive kernel on
+    4,096 of the sweeps. One untimed round first; then --runs rounds with the arms interleaved; kernel_ms from the HIP
+    events around each launch. One JSON line per arm: median / min / max ms, the ratio of the medians to the
+    closest-hit query's, the per-sweep ratio to the exhaustive kernel, nodes_visited and tris_tested per sweep, the
+    counters, and whether the fast kernel equals the exhaustive one on the 4,096 sweeps."""
+    import numpy as np
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        o, d, g, _ = point_sets(r, s, W, H)
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        bo = (o + d * torch.where(hit >= 0, t, torch.ones_like(t))[:, None]).contiguous()
+        bd = torch.randn(n, 3, generator=g)
+        bd = (bd / bd.norm(dim=1, keepdim=True)).cuda().contiguous()
+        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+        ext = float((v.max(0) - v.min(0)).max())
+        for label, so, sd in (("primary", o, d), ("bounce", bo, bd)):
+            pick = torch.randperm(n, generator=g)[:NS].cuda()
+            po, pd = so[pick].contiguous(), sd[pick].contiguous()
+            radii = {pct: torch.full((n,), ext * pct / 100, dtype=torch.float32, device="cuda")
+                     for pct in (0.0, 0.1, 1.0, 5.0)}
+            torch.cuda.synchronize()
+
+            def sweep(pct, c=so, m=sd, kernel="fast"):
+                res = r.sweep(c, m, radii[pct][:len(c)], kernel=kernel)
+                return r.sweep_info(), res, len(c)
+
+            def trace():
+                res = r.trace_rays(so, sd, kernel="fast")
+                return r.query_info(), res, n
+
+            arms = [("trace_rays", trace)]
+            for pct in radii:
+                arms.append((f"sweep_{pct}pct", lambda pct=pct: sweep(pct)))
+                arms.append((f"sweep_{pct}pct_exhaustive_4096", lambda pct=pct: sweep(pct, po, pd, "strict")))
+            same = {}
+            for pct in radii:  # the sample against the exhaustive kernel
+                x, y = sweep(pct, po, pd)[1], sweep(pct, po, pd, "strict")[1]
+                same[f"sweep_{pct}pct"] = all(bool((p.view(torch.int32) == q.view(torch.int32)).all())
+                                              for p, q in zip(x, y))
+            for _, fn in arms:  # the untimed round
+                fn()
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _, cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                line = {"scene": name, "set": label, "arm": k, "sweeps": cnt[k], "extent": round(ext, 4),
+                        "msweeps_s": round(cnt[k] / med[k] / 1e3, 2), "kernel_ms_median": round(med[k], 4),
+                        "kernel_ms_min": round(min(ms[k]), 4), "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_trace_rays": round((med[k] / cnt[k]) / (med["trace_rays"] / n), 3), "runs": a.runs,
+                        "info": {x: v for x, v in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                if k.startswith("sweep"):
+                    exh = k if k.endswith("_4096") else k + "_exhaustive_4096"
+                    line["per_sweep_ratio_to_exhaustive"] = round((med[k] / cnt[k]) / (med[exh] / NS), 6)
+                    line["sample_equals_exhaustive"] = same.get(k)
+                    line["nodes_visited_per_sweep"] = round(info["nodes_visited"] / cnt[k], 2)
+                    line["tris_tested_per_sweep"] = round(info["tris_tested"] / cnt[k], 2)
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
         r.close()
     if out:
         out.close()
