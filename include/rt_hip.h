@@ -690,6 +690,86 @@ typedef struct rt_sweep_info {
  * valid), RT_E_STATE before the first */
 int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info);
 
+/* Cut queries: per caller-supplied triangle the mesh triangles it crosses, how many, and the segment along which each
+ * pair crosses -- the query for the shape the scene itself is made of (mesh against mesh: the faces of a part, a tool
+ * or a cloth that cross the uploaded mesh; cutting: where a sheet crosses the surface, as segments that chain into
+ * cross-section polylines; clash checks of a placed component).
+ * Query i is a triangle with corners q0, q1, q2 (float32, as given). Its answer is
+ *   S_i = { j : X(q, triangle j) }, ordered by original triangle index ascending,
+ * and S_i is empty, decided before any walk, when any of the nine numbers is non-finite. No input value is an error.
+ * X is computed in float32 exactly as follows, on a triangle's record a = v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0), every
+ * operation rounded once, no FMA, dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z, u x v by the formula of rt_overlap_boxes'
+ * nrm, IEEE division, fminf / fmaxf with C semantics, a comparison with a NaN operand false. With b = a + e1,
+ * c = a + e2, f1 = q1 - q0, f2 = q2 - q0:
+ *   1. The gate. qlo = fminf(fminf(q0, q1), q2); qhi = fmaxf(fmaxf(q0, q1), q2)                  per component
+ *      tlo, thi: rt_overlap_boxes' step 1
+ *      X is false unless tlo.k <= qhi.k && thi.k >= qlo.k on all three axes k
+ *   2. The mesh triangle against the query's plane. nq = f1 x f2; dm_m = dot(nq, m - q0) for m = a, b, c
+ *      X is false when all three are > 0, all three are < 0, or all three are == 0 (a coplanar pair, a query of zero
+ *      area: neither is a member)
+ *   3. The query against the mesh triangle's plane. nm = e1 x e2; dq_m = dot(nm, q_m - a) for m = 0, 1, 2
+ *      the same three rejections
+ *   4. The line. D = nq x nm; k = 0; k = 1 if |D.y| > |D.x|; then k = 2 if |D.z| > |D.k|
+ *   5. Each triangle's interval on the line (Moller's interval test), from its corners v0..v2 (a, b, c; q0, q1, q2)
+ *      and their distances d0..d2 (dm; dq), with s_m = (d_m > 0) - (d_m < 0). The lone corner al is the first of
+ *        s0 == s1 && s0 != 0: 2;  s0 == s2 && s0 != 0: 1;  (s1 == s2 && s1 != 0) || s0 != 0: 0;  s1 != 0: 1;  else 2
+ *      and for the other two corners x = (al+1)%3, y = (al+2)%3:
+ *        lam_x = d_al / (d_al - d_x);  P_x = v_al + (v_x - v_al) * lam_x  per component;  t_x = P_x.k;  the same for y
+ *      The triangle's start point is P_x if t_x <= t_y, else P_y; its end point the other.
+ *      lo = fminf(t_x, t_y); hi = fmaxf(t_x, t_y)
+ *   6. Overlap. With [mlo, mhi] the mesh triangle's interval and [qlo_t, qhi_t] the query's:
+ *      X is true iff mlo <= qhi_t && qlo_t <= mhi (closed)
+ * The cut segment of a member: s0 = the query's start point if qlo_t > mlo, else the mesh triangle's start point;
+ * s1 = the query's end point if qhi_t < mhi, else the mesh triangle's end point. So s0.k <= s1.k up to NaN.
+ * Step 1 lets the walk drop a subtree by comparisons alone, with no margin. The set differs from the
+ * real-number one only within rounding of a grazing contact.
+ * Results: tri[i][0..max_tris) receives the first max_tris members of S_i by index (unused slots: -1);
+ * count[i] = min(|S_i|, max_tris), or |S_i| itself with count_all; max_tris = 0 with count_all is a pure count.
+ * The list form (offsets and list given) follows rt_overlap_boxes' rules: list[offsets[i] .. offsets[i+1]) receives
+ * members of S_i until it is full, in no stated order; the rest of the segment is not written, and nothing outside it
+ * is. With list_seg, a member written to list[p] has its s0 and s1 written to list_seg[p][0] and list_seg[p][1].
+ * Segments exist only in the list form; tri holds indices only.
+ * RT_KERNEL_STRICT tests every query against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view
+ * against the query's corner box and answers with the same bits; a scene without a wide view (RT_ACCEL_REFERENCE) runs
+ * the exhaustive loop under either.
+ * A cut query touches nothing a render or any other query owns. */
+#define RT_CUTS_MAX 16
+typedef struct rt_tris {
+    const float* tris;   /* device, [n][3][3] f32: q0, q1, q2 of every query */
+    const int* offsets;  /* device, [n + 1] i32, non-decreasing; nullable: given exactly when rt_cut_results.list is */
+    int n;               /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;        /* 0..RT_CUTS_MAX */
+    int count_all;       /* 0 / 1 */
+    int kernel;          /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_tris;
+typedef struct rt_cut_results { /* device pointers */
+    int* tri;        /* [n][max_tris]; required for max_tris > 0 */
+    int* count;      /* [n]; nullable for max_tris > 0, required for max_tris = 0 */
+    int* list;       /* [offsets[n]]; nullable: given exactly when rt_tris.offsets is */
+    float* list_seg; /* [offsets[n]][2][3] f32; nullable; only with list */
+} rt_cut_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null tris with n > 0, max_tris outside 0..RT_CUTS_MAX, max_tris > 0 without tri,
+ * max_tris = 0 without count_all and a count pointer, count_all not 0 / 1, offsets without list or list without
+ * offsets, list_seg without list, an unknown kernel, a negative n. */
+int rt_cut_triangles(rt_ctx* ctx, const rt_tris* tris, const rt_cut_results* out);
+typedef struct rt_cuts_info {
+    long long triangles, found; /* found: query triangles with a non-empty S_i */
+    long long stored, counted;  /* sums of min(|S_i|, max_tris) and of count[i] */
+    long long listed;           /* entries written to list: the sum of min(|S_i|, the segment's length) */
+    long long walked;           /* query triangles that walked the wide view */
+    long long exhaustive;       /* query triangles tested against every triangle: all valid ones under RT_KERNEL_STRICT
+                                   or without a wide view (an invalid one is in neither) */
+    long long empty;            /* triangles - found */
+    long long nodes_visited;    /* wide nodes decoded, summed over the queries */
+    long long pairs_tested;     /* evaluations of X, summed over the queries (exhaustive: queries x triangles) */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_cuts_info;
+/* counters of the last cut query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are not
+ * valid), RT_E_STATE before the first */
+int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

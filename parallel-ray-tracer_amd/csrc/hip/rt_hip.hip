@@ -40,6 +40,7 @@
 #include "rt_neighbours.hpp"
 #include "rt_overlap.hpp"
 #include "rt_sweep.hpp"
+#include "rt_cut.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -268,6 +269,11 @@ struct rt_ctx {
     hipEvent_t w_ev0 = nullptr, w_ev1 = nullptr;
     bool sweeps_run = false, w_launched = false;
     std::unordered_map<const void*, int> w_resident;  // resident workgroups of each k_sweep instantiation
+    // cut queries (rt_cut_triangles, rt_cut.hpp): their own again ([rtd::X_NCOUNT] counters, then the chunk counter)
+    unsigned long long* d_cutq = nullptr;
+    hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;
+    bool cuts_run = false, x_launched = false;
+    std::unordered_map<const void*, int> x_resident;  // resident workgroups of each k_cut instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3611,6 +3617,108 @@ extern "C" int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- cut queries (rt_cut.hpp)
+namespace {
+using XFn = void (*)(rtd::XArgs);
+// the smallest list capacity that holds max_tris (0: the counting build)
+XFn cut_kernel(int max_tris, bool strict) {
+    using rtd::k_cut;
+    if (max_tris == 0) return strict ? k_cut<0, true> : k_cut<0, false>;
+    if (max_tris <= 4) return strict ? k_cut<4, true> : k_cut<4, false>;
+    if (max_tris <= 8) return strict ? k_cut<8, true> : k_cut<8, false>;
+    return strict ? k_cut<16, true> : k_cut<16, false>;
+}
+}  // namespace
+
+extern "C" int rt_cut_triangles(rt_ctx* ctx, const rt_tris* r, const rt_cut_results* out) {
+    static_assert(RT_CUTS_MAX == rtd::CUTS_MAX && rtd::CUTS_MAX == rtd::OVERLAPS_MAX,
+                  "rt_hip.h, rt_cut.hpp and the capacities of rt_overlap.hpp's OState must agree");
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_cut_triangles: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_cut_triangles: null tris / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_cut_triangles: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_cut_triangles: negative triangle count");
+    if (r->max_tris < 0 || r->max_tris > RT_CUTS_MAX) return arg_err(ctx, "rt_cut_triangles: max_tris must be 0..16");
+    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_cut_triangles: count_all must be 0 or 1");
+    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_cut_triangles: max_tris = 0 needs count_all");
+    if ((r->offsets != nullptr) != (out->list != nullptr))
+        return arg_err(ctx, "rt_cut_triangles: offsets and list are given together or not at all");
+    if (out->list_seg && !out->list) return arg_err(ctx, "rt_cut_triangles: list_seg needs a list");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && !r->tris) return arg_err(ctx, "rt_cut_triangles: null tris");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri) return arg_err(ctx, "rt_cut_triangles: max_tris > 0 needs a tri output");
+    if (r->n > 0 && r->max_tris == 0 && !out->count)
+        return arg_err(ctx, "rt_cut_triangles: a counting query needs a count output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::X_NCOUNT + 1);
+    if (!ctx->d_cutq) HIPC(hipMalloc((void**)&ctx->d_cutq, cbytes));
+    if (!ctx->x_ev0) HIPC(hipEventCreate(&ctx->x_ev0));
+    if (!ctx->x_ev1) HIPC(hipEventCreate(&ctx->x_ev1));
+    HIPC(hipMemsetAsync(ctx->d_cutq, 0, cbytes, ctx->stream));
+    ctx->cuts_run = true;
+    ctx->x_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::XArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.tris = r->tris;
+    A.offsets = r->offsets;
+    A.tri = r->max_tris > 0 ? out->tri : nullptr;
+    A.count = out->count;
+    A.list = out->list;
+    A.list_seg = out->list_seg;
+    A.counters = ctx->d_cutq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_cutq + rtd::X_NCOUNT);
+    A.n = r->n;
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    const XFn k = cut_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->x_resident.find((const void*)k);
+    if (res == ctx->x_resident.end()) res = ctx->x_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->x_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->x_ev1, ctx->stream));
+    ctx->x_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->cuts_run) {
+        ctx->err = "rt_get_cuts_info: no cut query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::X_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_cutq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->triangles = (long long)c[rtd::X_TRIS];
+    info->found = (long long)c[rtd::X_FOUND];
+    info->stored = (long long)c[rtd::X_STORED];
+    info->counted = (long long)c[rtd::X_COUNTED];
+    info->listed = (long long)c[rtd::X_LISTED];
+    info->walked = (long long)c[rtd::X_WALKED];
+    info->exhaustive = (long long)c[rtd::X_EXH];
+    info->empty = (long long)c[rtd::X_EMPTY];
+    info->nodes_visited = (long long)c[rtd::X_NODES];
+    info->pairs_tested = (long long)c[rtd::X_PAIRS];
+    info->stack_overflows = (long long)c[rtd::X_ERR];
+    if (ctx->x_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->x_ev0, ctx->x_ev1));
+    if (c[rtd::X_ERR]) {
+        ctx->err = "rt_get_cuts_info: the query's traversal stack overflowed " + std::to_string(c[rtd::X_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4494,6 +4602,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_swq) (void)hipFree(ctx->d_swq);
     if (ctx->w_ev0) (void)hipEventDestroy(ctx->w_ev0);
     if (ctx->w_ev1) (void)hipEventDestroy(ctx->w_ev1);
+    if (ctx->d_cutq) (void)hipFree(ctx->d_cutq);
+    if (ctx->x_ev0) (void)hipEventDestroy(ctx->x_ev0);
+    if (ctx->x_ev1) (void)hipEventDestroy(ctx->x_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

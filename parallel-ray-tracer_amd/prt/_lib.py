@@ -230,6 +230,27 @@ class SweepInfo(ctypes.Structure):  # rt_sweep_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+CUTS_MAX = 16  # RT_CUTS_MAX
+
+
+class Tris(ctypes.Structure):  # rt_tris
+    _fields_ = [("tris", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("max_tris", ctypes.c_int), ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class CutResults(ctypes.Structure):  # rt_cut_results
+    _fields_ = [("tri", ctypes.c_void_p), ("count", ctypes.c_void_p), ("list", ctypes.c_void_p),
+                ("list_seg", ctypes.c_void_p)]
+
+
+class CutsInfo(ctypes.Structure):  # rt_cuts_info
+    _fields_ = [("triangles", ctypes.c_longlong), ("found", ctypes.c_longlong), ("stored", ctypes.c_longlong),
+                ("counted", ctypes.c_longlong), ("listed", ctypes.c_longlong), ("walked", ctypes.c_longlong),
+                ("exhaustive", ctypes.c_longlong), ("empty", ctypes.c_longlong), ("nodes_visited", ctypes.c_longlong),
+                ("pairs_tested", ctypes.c_longlong), ("stack_overflows", ctypes.c_longlong),
+                ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -359,6 +380,8 @@ def hip():
         L.rt_get_overlaps_info.argtypes = [ctypes.c_void_p, P(OverlapsInfo)]
         L.rt_sweep_spheres.argtypes = [ctypes.c_void_p, P(Spheres), P(SweepResults)]
         L.rt_get_sweep_info.argtypes = [ctypes.c_void_p, P(SweepInfo)]
+        L.rt_cut_triangles.argtypes = [ctypes.c_void_p, P(Tris), P(CutResults)]
+        L.rt_get_cuts_info.argtypes = [ctypes.c_void_p, P(CutsInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

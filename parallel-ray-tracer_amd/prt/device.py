@@ -771,6 +771,96 @@ class Renderer:
         key, _ = torch.sort(seg * n_tris + tris.to(torch.int64))  # (segment-major, index ascending within each)
         return offsets, (key - seg * n_tris).to(torch.int32)
 
+    def _tris(self, tris):
+        """(pointer, n) of an [n, 3, 3] float32 contiguous tensor on this device, or of a raw pointer given as
+        tris=(pointer, n)"""
+        import torch
+        if isinstance(tris, tuple):
+            pt, n = tris if len(tris) == 2 else (None, None)
+            if not isinstance(pt, int) or not isinstance(n, int) or isinstance(n, bool) or n < 0:
+                raise RtError("tris: a raw pointer is given as tris=(pointer, n)")
+            return pt, n
+        if not isinstance(tris, torch.Tensor):
+            raise RtError(f"tris: expected a torch tensor or a raw (pointer, n), got {type(tris).__name__}")
+        if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3):
+            raise RtError(f"tris: shape {tuple(tris.shape)}, expected [n, 3, 3]")
+        n = tris.shape[0]
+        return _ptr(tris, "tris", 9 * n, (torch.float32,), self.device), n
+
+    def cuts(self, tris, k=8, count_all=False, kernel="auto", tri=None, count=None):
+        """rt_cut_triangles: per caller-supplied triangle q0, q1, q2 the triangles of the scene that it crosses -- the
+        first k by original triangle index of S_i = { j : X(q, triangle j) }, X the float32 triangle-triangle test
+        include/rt_hip.h states (a coplanar pair and a zero-area query are no members) -> (tri [n, k] int32, -1 in
+        unused slots; count [n] int32 = min(|S_i|, k), or |S_i| itself with count_all=True). tris: an [n, 3, 3]
+        float32 contiguous tensor on this device (or a raw pointer: tris=(pointer, n)); a non-finite number gives the
+        empty set. k: 0..16; 0 with count_all=True is a pure count (tri comes back empty). kernel="strict" tests every
+        triangle (the checker), "fast" / "auto" walks the full wide view with the same answer. tri / count: optional
+        outputs (allocated when not given). cuts_csr gives every query's full set and the cut segments. Asynchronous
+        on the renderer's stream: sync() or cuts_info() before the results are read on another stream."""
+        import torch
+        i32 = (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.CUTS_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.CUTS_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        pt, n = self._tris(tris)
+        for x, what, m in ((tri, "tri", n * k), (count, "count", n)):
+            _ptr(x, what, m, i32, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        res = _lib.CutResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                              _ptr(count, "count", n, i32, self.device), None, None)
+        q = _lib.Tris(pt, None, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_cut_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_cut_triangles")
+        return tri, count
+
+    def cuts_info(self):
+        """rt_get_cuts_info: the last cut query's counters (triangles, found, stored, counted, listed, walked,
+        exhaustive, empty, nodes_visited, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed
+        its stack"""
+        i = _lib.CutsInfo()
+        self._chk(_L.rt_get_cuts_info(self._ctx, ctypes.byref(i)), "rt_get_cuts_info")
+        return {f: getattr(i, f) for f, _ in _lib.CutsInfo._fields_}
+
+    def cuts_csr(self, tris, segments=True, kernel="auto"):
+        """every query triangle's full S_i, in index order, with the cut segments -> (offsets [n + 1] int32, tri
+        [offsets[n]] int32, seg [offsets[n], 2, 3] float32; seg is None with segments=False): query i crosses the
+        triangles tri[offsets[i]:offsets[i + 1]], ascending, along seg[p] = (s0, s1) for the pair at p. Two launches
+        of rt_cut_triangles -- a pure count, then the list form into the counts' prefix sums -- and one sort that puts
+        each segment of the list in index order, the cut segments permuted alongside. Synchronises (the total is read
+        on the host); refuses a total of 2^31 or more. tris and kernel as cuts takes them."""
+        import torch
+        pt, n = self._tris(tris)
+        dev = f"cuda:{self.device}"
+        kern = KERNELS.get(kernel, kernel)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        q = _lib.Tris(pt, None, n, 0, 1, kern)
+        res = _lib.CutResults(None, _ptr(count, "count", n, (torch.int32,), self.device), None, None)
+        self._chk(_L.rt_cut_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_cut_triangles")
+        self.cuts_info()  # (synchronises the renderer's stream with torch's; raises on an overflowed stack)
+        ends = torch.cumsum(count, 0, dtype=torch.int64)
+        total = int(ends[-1]) if n else 0
+        if total >= 2 ** 31:
+            raise RtError(f"cuts_csr: {total} entries in all, int32 offsets hold fewer than 2^31: split the triangles")
+        offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        offsets[1:] = ends.to(torch.int32)
+        idx = torch.empty(total, dtype=torch.int32, device=dev)
+        seg = torch.empty((total, 2, 3), dtype=torch.float32, device=dev) if segments else None
+        if total == 0:
+            return offsets, idx, seg
+        torch.cuda.current_stream(self.device).synchronize()  # (offsets is torch's work, the query runs on ours)
+        q = _lib.Tris(pt, offsets.data_ptr(), n, 0, 1, kern)
+        res = _lib.CutResults(None, count.data_ptr(), idx.data_ptr(), seg.data_ptr() if segments else None)
+        self._chk(_L.rt_cut_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_cut_triangles")
+        self.cuts_info()
+        n_tris = self.scene_info()["n_triangles"]
+        row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), count.to(torch.int64))
+        key, order = torch.sort(row * n_tris + idx.to(torch.int64))  # (query-major, index ascending within each)
+        return offsets, (key - row * n_tris).to(torch.int32), seg[order] if segments else None
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

@@ -15,14 +15,16 @@ The fast and the strict kernel answer with the same bits (checked here on every 
 closest-hit query (hits_mode below), --mode nearest rt_nearest_points (nearest_mode below),
 --mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below), --mode overlap
 rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below), --mode sweep
-rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below).
+rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below), --mode cuts
+rt_cut_triangles beside rt_overlap_boxes on the query triangles' corner boxes (cuts_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
        python tools/query_bench.py --mode nearest [--runs 7] [--out profiles/nearest_bench_<md5>.jsonl]
        python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]
        python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode cuts [--runs 5] [--out profiles/cuts_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -39,16 +41,17 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep"],
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
                          "nearest: rt_nearest_points beside the closest-hit query (nearest_mode); "
                          "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode); "
                          "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode); "
-                         "sweep: rt_sweep_spheres beside the closest-hit query (sweep_mode)")
+                         "sweep: rt_sweep_spheres beside the closest-hit query (sweep_mode); "
+                         "cuts: rt_cut_triangles beside rt_overlap_boxes on the corner boxes (cuts_mode)")
     ap.add_argument("--out", default=None,
-                    help="nearest, neighbours, overlap, sweep: also append the raw lines to this file")
+                    help="nearest, neighbours, overlap, sweep, cuts: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -68,6 +71,8 @@ def main():
         return overlap_mode(a, md5)
     if a.mode == "sweep":
         return sweep_mode(a, md5)
+    if a.mode == "cuts":
+        return cuts_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -647,6 +652,118 @@ def sweep_mode(a, md5):
                 if out:
                     out.write(json.dumps(line) + "\n")
                     out.flush()
+        r.close()
+    if out:
+        out.close()
+
+
+def cuts_mode(a, md5):
+    """--mode cuts: per scene, rt_cut_triangles on W x H query triangles (1920 x 1080 = 2,073,600 by
+    default) in two shapes: triangles centred on the hit points of the camera's primary rays (a missing ray's centre
+    lies at t = 1) whose corners are the centre plus size * (a standard normal 3 x 3 draw with the corner mean
+    removed), with sizes of 0.1 %, 1 % and 5 % of the scene's extent (its box's longest side), and a prt.tris.sheet
+    through the middle of the scene's box, tilted by a tenth of the extent along both sides (1440 x 720 cells at the
+    default size). Per set: the pure count (k = 0, count_all), k = 8 (tri and count) and the CSR form with its segments
+    (cuts_csr: the count, the list form and the sort; wall-clock ms around the call, skipped when the sets hold more
+    than 2^26 entries in all), beside rt_overlap_boxes' pure count on the same triangles' corner boxes (the same walk
+    and the same cull: the ratio prices the pair test), and the exhaustive kernel's count on 4,096 of the queries. One
+    untimed round first; then --runs rounds with the arms interleaved; kernel_ms from the HIP events around each
+    launch. One JSON line per arm: median / min / max ms, the ratio of the medians to the box count's, the per-query
+    ratio to the exhaustive kernel, nodes_visited and pairs_tested per query, the counters, and whether the fast kernel
+    equals the exhaustive one on the 4,096 queries (count, k = 8, and the CSR form with its segments' bits)."""
+    import time
+
+    import numpy as np
+    import torch
+    from prt import device, host, tris
+    W, H, n = a.width, a.height, a.width * a.height
+    NS, CSR_CAP = 4096, 1 << 26
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        o, d, g, _ = point_sets(r, s, W, H)
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        ctr = (o + d * torch.where(hit >= 0, t, torch.ones_like(t))[:, None]).contiguous()
+        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+        slo, shi = v.min(0), v.max(0)
+        ext = float((shi - slo).max())
+        off = torch.randn(n, 3, 3, generator=g)
+        off = (off - off.mean(dim=1, keepdim=True)).cuda()
+        sets = [(f"hit_points_{pct}pct", (ctr[:, None, :] + off * (ext * pct / 100)).contiguous(), ext * pct / 100)
+                for pct in (0.1, 1.0, 5.0)]
+        dims = (1440, 720) if n == 2073600 else (W, max(H // 2, 1))
+        mid = (slo + shi) / 2
+        su = np.array([shi[0] - slo[0], 0.0, 0.1 * ext], np.float32)
+        sv = np.array([0.0, shi[1] - slo[1], 0.1 * ext], np.float32)
+        sheet = tris.sheet(np.array([slo[0], slo[1], mid[2] - 0.1 * ext], np.float32), su, sv, dims)
+        sets.append((f"sheet_{dims[0]}x{dims[1]}", sheet, float(max(su[0] / dims[0], sv[1] / dims[1]))))
+        for label, q, size in sets:
+            m = len(q)
+            pick = torch.randperm(m, generator=g)[:NS].cuda()
+            qs = q[pick].contiguous()
+            lo, hi = q.min(dim=1).values.contiguous(), q.max(dim=1).values.contiguous()
+            torch.cuda.synchronize()
+
+            def cuts(k, p=q, kernel="fast"):
+                res = r.cuts(p, k=k, count_all=k == 0, kernel=kernel)
+                return r.cuts_info(), res, len(p)
+
+            def box_count():
+                res = r.overlaps(lo, hi, k=0, count_all=True)
+                return r.overlaps_info(), res, m
+
+            def csr(p=q, kernel="fast"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = r.cuts_csr(p, kernel=kernel)
+                torch.cuda.synchronize()
+                info = dict(r.cuts_info())
+                info["kernel_ms"] = (time.perf_counter() - t0) * 1e3  # (wall clock: two launches, a scan and a sort)
+                return info, res, len(p)
+
+            total = int(cuts(0)[1][1].sum(dtype=torch.int64))
+            arms = [("cut_count", lambda: cuts(0)), ("cut_k8", lambda: cuts(8)), ("box_count", box_count),
+                    ("cut_count_exhaustive_4096", lambda: cuts(0, qs, "strict"))]
+            if total <= CSR_CAP:
+                arms.append(("cut_csr", csr))
+            same = {}
+            for k in (0, 8):  # the sample against the exhaustive kernel
+                x, y = cuts(k, qs)[1], cuts(k, qs, "strict")[1]
+                same["cut_count" if k == 0 else "cut_k8"] = all(bool((p == w).all()) for p, w in zip(x, y))
+            x, y = csr(qs)[1], csr(qs, "strict")[1]
+            same["cut_csr"] = all(bool((p.view(torch.int32) == w.view(torch.int32)).all()) for p, w in zip(x, y))
+            for _, fn in arms:  # the untimed round
+                fn()
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _, cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                tested = info["tris_tested"] if k == "box_count" else info["pairs_tested"]
+                line = {"scene": name, "set": label, "arm": k, "queries": cnt[k], "size": round(size, 6),
+                        "set_entries": total, "mqueries_s": round(cnt[k] / med[k] / 1e3, 2),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_box_count": round((med[k] / cnt[k]) / (med["box_count"] / m), 3),
+                        "per_query_ratio_to_exhaustive": round((med[k] / cnt[k]) /
+                                                               (med["cut_count_exhaustive_4096"] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same.get(k),
+                        "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
+                        "tests_per_query": round(tested / cnt[k], 2),
+                        "info": {x: w for x, w in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+            if total > CSR_CAP:
+                print(json.dumps({"scene": name, "set": label, "arm": "cut_csr", "skipped": "set_entries above the cap",
+                                  "set_entries": total, "cap": CSR_CAP}), flush=True)
         r.close()
     if out:
         out.close()
