@@ -57,7 +57,13 @@ clean:
 # exhaustive check of rtd::rcp_ieee against IEEE division (test infrastructure, tests/test_gpu_rcp.py)
 RCP_CHECK := tools/rcp/rcp_exhaustive
 hip: $(RCP_CHECK)
-$(RCP_CHECK): tools/rcp/rcp_exhaustive.hip $(CSRC)/hip/rt_device.hpp
+$(RCP_CHECK): tools/rcp/rcp_exhaustive.hip $(CSRC)/hip/rt_device.hpp $(CSRC)/hip/rt_exact.hpp
+	$(HIPCC) $(HIP_FLAGS) -o $@ $<
+
+# exhaustive checks of rt_exact.hpp's device forms against `/` and sqrtf (test infrastructure, tests/test_gpu_exact_forms.py)
+EXACT_CHECK := tools/exact/exact_exhaustive
+hip: $(EXACT_CHECK)
+$(EXACT_CHECK): tools/exact/exact_exhaustive.hip $(CSRC)/hip/rt_device.hpp $(CSRC)/hip/rt_exact.hpp
 	$(HIPCC) $(HIP_FLAGS) -o $@ $<
 
 # Sanitizer build of the host library (SURVEY §5 "race detection / sanitizers"): librt_host.so -- the OBJ/MTL parser

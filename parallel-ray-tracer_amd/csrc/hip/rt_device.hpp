@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rt_exact.hpp"
+
 namespace rtd {
 
 constexpr float EPS = 1e-3f;             // EPSILON, cpu/src/raytracer.c:19
@@ -140,9 +142,7 @@ static_assert(sizeof(DWide) == 32 && sizeof(DScene) == 256 && sizeof(KArgs) == 5
               "kernel-argument layout changed: update the pinned sizes only after checking both passes agree");
 
 // ---------------------------------------------------------------- vec_t arithmetic (cpu/src/vec.c)
-struct v3 {
-    float x, y, z;
-};
+using v3 = rtx::f3;  // (float x, y, z; rt_exact.hpp, which g++ compiles alone)
 __device__ __forceinline__ v3 mk(float x, float y, float z) { return v3{x, y, z}; }
 __device__ __forceinline__ v3 add(v3 a, v3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ v3 sub(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -155,6 +155,29 @@ __device__ __forceinline__ v3 cross(v3 a, v3 b) {
 }
 __device__ __forceinline__ v3 normalize(v3 a) { return dvs(a, mag(a)); }
 __device__ __forceinline__ v3 xyz(float4 f) { return mk(f.x, f.y, f.z); }
+
+// The frame kernels' code around the walks (ray formation, shading, level setup) divides and takes roots through
+// rt_exact.hpp's short forms: the same bits as `/` and sqrtf for every input, in about a third of the instructions
+// inside their guard ranges. PRT_EXACT_NORM=0: dvs / mag / normalize as above, everywhere.
+#ifndef PRT_EXACT_NORM
+#define PRT_EXACT_NORM 1
+#endif
+constexpr bool EXACT_NORM = PRT_EXACT_NORM != 0;
+__device__ __forceinline__ v3 dvs_x(v3 a, float s) { return EXACT_NORM ? rtx::div3(a, s) : dvs(a, s); }
+__device__ __forceinline__ v3 normalize_x(v3 a) { return EXACT_NORM ? rtx::normalize3(a) : normalize(a); }
+// mg = mag(a), a / mg
+__device__ __forceinline__ v3 normalize_mag_x(v3 a, float& mg) {
+    if (EXACT_NORM) return rtx::normalize_mag(a, mg);
+    mg = mag(a);
+    return dvs(a, mg);
+}
+// mag(a) > 0 (raytracer.c:168) without the root: a.a is a sum of squares, so it is >= 0 or NaN, and sqrtf of it is > 0
+// exactly when it is (the root of the smallest denormal is a normal number; sqrtf(+-0) = +-0; a NaN compares false
+// either way)
+__device__ __forceinline__ bool mag_positive(v3 a) {
+    if (EXACT_NORM) return a.x * a.x + a.y * a.y + a.z * a.z > 0.0f;
+    return mag(a) > 0.0f;
+}
 
 // One finished pixel (o = frame-relative output index) to the frame's outputs: the f32 vec_t pixel
 // (main.c:39) and/or its BMP quantisation vec_to_bgra (cpu/src/bmp_writer.c:88-95; as k_bgra, but in
@@ -242,11 +265,18 @@ struct RayPre {
 // could then reject a box the ray passes through): such components are replaced by +1e-20, for which
 // the slab degenerates to [-huge, +huge] (ray inside) or a same-signed huge pair (ray outside).
 __device__ __forceinline__ float safe_dir(float x) { return __builtin_fabsf(x) < 1e-20f ? 1e-20f : x; }
+// UNIT: d is a normalize result (every |d_i| <= 1 up to rounding), so the reciprocal needs no division above 2^125
+// and no branch (rtx::rcp_small: rcp_ieee's other arm, the same bits). PRT_RCP_UNIT=0: rcp_ieee everywhere.
+#ifndef PRT_RCP_UNIT
+#define PRT_RCP_UNIT 1
+#endif
+template <bool UNIT = false>
 __device__ __forceinline__ RayPre ray_pre(v3 o, v3 d) {
     RayPre p;
-    p.ix = rcp_ieee(safe_dir(d.x));
-    p.iy = rcp_ieee(safe_dir(d.y));
-    p.iz = rcp_ieee(safe_dir(d.z));
+    constexpr bool SMALL = UNIT && PRT_RCP_UNIT != 0;
+    p.ix = SMALL ? rtx::rcp_small(safe_dir(d.x)) : rcp_ieee(safe_dir(d.x));
+    p.iy = SMALL ? rtx::rcp_small(safe_dir(d.y)) : rcp_ieee(safe_dir(d.y));
+    p.iz = SMALL ? rtx::rcp_small(safe_dir(d.z)) : rcp_ieee(safe_dir(d.z));
     p.ox = o.x * p.ix;
     p.oy = o.y * p.iy;
     p.oz = o.z * p.iz;

@@ -480,8 +480,25 @@ __device__ __forceinline__ void count_step(Ctr& c, bool shadow) {
     c.q3 += b == 2 ? f : 0u;
     c.q4 += b == 3 ? f : 0u;
 #endif
+#if !defined(PRT_DIAG_REFILL)
     if (c.hist && f) atomicAdd(c.hist + (shadow ? 16u : 0u) + 4u * (c.lvl < 3u ? c.lvl : 3u) + b, 1u);
+#endif
 }
+// Diagnostics build (PRT_DEFS=-DPRT_DIAG_REFILL): the histogram's slots count the pool kernels' path levels per tile
+// instead of wave steps, one per wave and event (tools/stream_budget.py multiplies its per-level parts by them):
+// [0][level][0] closest levels run (loop iterations with a lane alive), [1][level][0] iterations of the shading loop,
+// [1][level][1] of which some lane shades a hit (the others only write the miss colour and leave).
+#ifdef PRT_DIAG_REFILL
+#define PRT_LEVEL_CNT(c, kind, it, bin)                                                                        \
+    do {                                                                                                       \
+        if (COUNT && (c).hist && first_active_lane())                                                          \
+            atomicAdd((c).hist + 16u * (kind) + 4u * ((unsigned)(it) < 3u ? (unsigned)(it) : 3u) + (bin), 1u); \
+    } while (0)
+#else
+#define PRT_LEVEL_CNT(c, kind, it, bin) \
+    do {                                \
+    } while (0)
+#endif
 
 // Plane decoding (rt_wide.cpp): plane = fmaf(2^e, QBIAS + q, p). QBIAS + q is an f16 integer with the bits
 // 0x6400 | q, so one v_perm_b32 makes two of them from two plane bytes of a node word (the constant bytes 0x64 from
@@ -568,8 +585,11 @@ __device__ __forceinline__ float fma_half_clamp(unsigned h2, int hi, float k, fl
 #define PRT_SHADOW_CLAMP 1
 #endif
 constexpr bool SHADOW_CLAMP = PRT_SHADOW_CLAMP != 0;
+// UNIT: ray_pre's (the pool's ray formation, whose d is a normalize result). (1.0f / span stays a division: through
+// rcp_ieee it measured as nothing)
+template <bool UNIT = false>
 __device__ __forceinline__ RayPre ray_pre_shadow(v3 o, v3 d, float reach) {
-    RayPre p = ray_pre(o, d);
+    RayPre p = ray_pre<UNIT>(o, d);
     if (SHADOW_CLAMP) {
         // s <= 1 / (reach - BOX_TMIN) up to one rounding, then 2^-20 smaller: the [0, 1] of t' covers [BOX_TMIN, reach]
         // (reach <= BOX_TMIN: nothing can occlude; any positive scale is then conservative)
@@ -1494,8 +1514,8 @@ __device__ __forceinline__ bool path_shade(const DScene& s, int bounces, int it,
         // values (pure functions of ip, n, d, the material and the light), fewer of them live across the walk
         const v3 Lp = xyz(s.lights[2 * j]);
         v3 l = sub(Lp, ip);
-        float mg = mag(l);
-        l = dvs(l, mg);
+        float mg;
+        l = normalize_mag_x(l, mg);
         mg *= mg;
         const v3 tmp = sub(ip, Lp), tmp2 = sub(Lp, ip);
         const float ld2 = dot(tmp, tmp);
@@ -1511,18 +1531,19 @@ __device__ __forceinline__ bool path_shade(const DScene& s, int bounces, int it,
         const v3 kl = xyz(s.lights[2 * j + 1]);
         const v3 ks = xyz(s.mats[3 * m]), kd = xyz(s.mats[3 * m + 1]);
         const float ndl = dot(n, l);
-        const v3 h = normalize(add(l, v));  // lambert_blinn, raytracer.c:21-33
+        const v3 h = normalize_x(add(l, v));  // lambert_blinn, raytracer.c:21-33
         const float coeff = fmaxf(0.0f, dot(n, h));
         const v3 cr = mk(kd.x * fmaxf(0.0f, ndl) + ks.x * coeff, kd.y * fmaxf(0.0f, ndl) + ks.y * coeff,
                          kd.z * fmaxf(0.0f, ndl) + ks.z * coeff);
         const float fV = (float)V;
-        col.x = col.x + fV * kl.x * cr.x / mg;
-        col.y = col.y + fV * kl.y * cr.y / mg;
-        col.z = col.z + fV * kl.z * cr.z / mg;
+        const v3 cq = dvs_x(mk(fV * kl.x * cr.x, fV * kl.y * cr.y, fV * kl.z * cr.z), mg);
+        col.x = col.x + cq.x;
+        col.y = col.y + cq.y;
+        col.z = col.z + cq.z;
     }
     const v3 dd = mul(v, -1.0f);  // raytracer.c:163-166
     const v3 ns = mul(n, 2.0f * __builtin_fabsf(dot(dd, n)));
-    const v3 r = normalize(add(dd, ns));
+    const v3 r = normalize_x(add(dd, ns));
     if constexpr (PB) {
         pb[it * 64] = make_float4(col.x, col.y, col.z, __int_as_float(m));
     } else {
@@ -1530,7 +1551,7 @@ __device__ __forceinline__ bool path_shade(const DScene& s, int bounces, int it,
         seti<MAXB>(mats, it, m);
     }
     const v3 kr = xyz(s.mats[3 * m + 2]);
-    if (!(mag(kr) > 0.0f)) {  // raytracer.c:168
+    if (!mag_positive(kr)) {  // raytracer.c:168
         L = it + 1;
         tail = false;
         return true;

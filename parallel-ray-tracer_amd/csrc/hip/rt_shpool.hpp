@@ -35,7 +35,8 @@ __device__ __forceinline__ unsigned mbcnt64(unsigned long long m) {
 
 // Diagnostics build (PRT_DEFS=-DPRT_DIAG_REFILL): under RT_FLAG_COUNTERS the lane-count bins count the pool's refill
 // instead of wave steps -- q1 refill rounds, q2 iterations of the cursor hand-out's loop (the list form has none),
-// q3 lanes refilled, q4 job lists built (tools/stream_budget.py prices them).
+// q3 lanes refilled, q4 job lists built (tools/stream_budget.py prices them); the histogram's slots count the path
+// levels (PRT_LEVEL_CNT, rt_kernels.hpp).
 #ifdef PRT_DIAG_REFILL
 #define PRT_REFILL_CNT(c, q, n) \
     do {                        \
@@ -256,8 +257,8 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
             const v3 ipo = xyz(lvl[wo & 511]);  // (64 level + owner)
             const v3 Lp = xyz(s.lights[2 * (wo >> 9)]);
             v3 l = sub(Lp, ipo);
-            const float mg = mag(l);
-            l = dvs(l, mg);
+            float mg;
+            l = normalize_mag_x(l, mg);
             const v3 tmp = sub(ipo, Lp);
             ld2 = dot(tmp, tmp);
             o = ipo;
@@ -271,7 +272,7 @@ __device__ __forceinline__ void shadow_pool(const DScene& s, OKM okm, float4* lv
                 // component, a square loses the sign, and mag() and dot() add the three squares in the same order.
                 // (The cursor form, which k_shade's pool shares, keeps its expression; PRT_REACH_MAG=0: everywhere.)
                 reach = LIST && REACH_MAG ? shadow_reach_mag(o, mg) : shadow_reach(o, ld2);
-                p = ray_pre_shadow(o, d, reach);
+                p = ray_pre_shadow<true>(o, d, reach);  // (d = l, a normalize result)
                 oct = (p.ix < 0.0f ? 1u : 0u) | (p.iy < 0.0f ? 2u : 0u) | (p.iz < 0.0f ? 4u : 0u);
                 best = FMAX;
                 sp = 0;
@@ -416,6 +417,7 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
         const unsigned na = popc_wave(alive);
         if (na == 0) break;
         if (COUNT) c.lvl = (unsigned)it;
+        PRT_LEVEL_CNT(c, 0, it, 0);
         if (it == 0) u.prim += na;
         else u.refl += na;
         int hit = -1;  // the hit triangle (original index) | nd << 31 ... as two fields below
@@ -461,6 +463,8 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
             u.skip -= u.shad - sh0;
         }
         if (hit >= 0) {  // raytracer.c:144-172 as path_step, the lights' visibility from the pool
+            PRT_LEVEL_CNT(c, 1, it, 0);
+            PRT_LEVEL_CNT(c, 1, it, 1);
             const float4 e = pb[it * 64];
             const v3 ip = xyz(e);
             const unsigned vis = __float_as_uint(e.w) & okm;
@@ -473,28 +477,29 @@ __device__ __forceinline__ v3 trace_path_shp(const KArgs& A, bool alive, v3 o, v
             for (int j = 0; j < s.n_lights; ++j) {
                 const v3 Lp = xyz(s.lights[2 * j]);
                 v3 l = sub(Lp, ip);
-                float mg = mag(l);
-                l = dvs(l, mg);
+                float mg;
+                l = normalize_mag_x(l, mg);
                 mg *= mg;
                 const int V = (int)((vis >> j) & 1u);  // 0 behind the surface (okm), else the shadow ray's answer
                 const v3 kl = xyz(s.lights[2 * j + 1]);
                 const v3 ks = xyz(s.mats[3 * m]), kd = xyz(s.mats[3 * m + 1]);
                 const float ndl = dot(n, l);
-                const v3 h = normalize(add(l, v));
+                const v3 h = normalize_x(add(l, v));
                 const float coeff = fmaxf(0.0f, dot(n, h));
                 const v3 cr = mk(kd.x * fmaxf(0.0f, ndl) + ks.x * coeff, kd.y * fmaxf(0.0f, ndl) + ks.y * coeff,
                                  kd.z * fmaxf(0.0f, ndl) + ks.z * coeff);
                 const float fV = (float)V;
-                col.x = col.x + fV * kl.x * cr.x / mg;
-                col.y = col.y + fV * kl.y * cr.y / mg;
-                col.z = col.z + fV * kl.z * cr.z / mg;
+                const v3 cq = dvs_x(mk(fV * kl.x * cr.x, fV * kl.y * cr.y, fV * kl.z * cr.z), mg);
+                col.x = col.x + cq.x;
+                col.y = col.y + cq.y;
+                col.z = col.z + cq.z;
             }
             const v3 dd = mul(v, -1.0f);
             const v3 ns = mul(n, 2.0f * __builtin_fabsf(dot(dd, n)));
-            const v3 r = normalize(add(dd, ns));
+            const v3 r = normalize_x(add(dd, ns));
             pb[it * 64] = make_float4(col.x, col.y, col.z, __int_as_float(m));
             const v3 kr = xyz(s.mats[3 * m + 2]);
-            if (!(mag(kr) > 0.0f)) {  // raytracer.c:168
+            if (!mag_positive(kr)) {  // raytracer.c:168
                 L = it + 1;
                 tail = false;
                 alive = false;
@@ -572,6 +577,7 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
         const unsigned na = popc_wave(alive);
         if (na == 0) break;
         if (COUNT) c.lvl = (unsigned)it;
+        PRT_LEVEL_CNT(c, 0, it, 0);
         if (it == 0) u.prim += na;
         else u.refl += na;
         bool hitl = false;
@@ -613,9 +619,9 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
                 pb[it * 64] = make_float4(ip.x, ip.y, ip.z, __uint_as_float(0u));
                 hid[it * 64] = orig | (nd ? (1 << 30) : 0);
                 const v3 ns = mul(n, 2.0f * __builtin_fabsf(dot(d, n)));  // (dd = -(-d) = d exactly)
-                const v3 r = normalize(add(d, ns));
+                const v3 r = normalize_x(add(d, ns));
                 const v3 kr = xyz(s.mats[3 * m + 2]);
-                if (!(mag(kr) > 0.0f)) {  // raytracer.c:168
+                if (!mag_positive(kr)) {  // raytracer.c:168
                     L = it + 1;
                     tail = false;
                     alive = false;
@@ -643,11 +649,13 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
     v3 dl = d0;  // level i's direction: the primary one, then each level's reflection
     // <budget:shading>
     for (int it = 0; it < L; ++it) {  // the levels' colours (raytracer.c:144-160 as path_step), in order
+        PRT_LEVEL_CNT(c, 1, it, 0);
         const int h = hid[it * 64];
         if (h < 0) {  // a miss (the path's last level): the background
             pb[it * 64] = make_float4(0.0f + amb.x, 0.0f + amb.y, 0.0f + amb.z, __int_as_float(0));
             break;
         }
+        PRT_LEVEL_CNT(c, 1, it, 1);
         const float4 e = pb[it * 64];
         const v3 ip = xyz(e);
         const unsigned vis = __float_as_uint(e.w) & ((unsigned)(okm >> (8 * it)) & 0xFFu);
@@ -661,25 +669,26 @@ __device__ __forceinline__ v3 trace_path_dfr(const ARGS& A, bool alive, v3 o, v3
         for (int j = 0; j < s.n_lights; ++j) {
             const v3 Lp = xyz(s.lights[2 * j]);
             v3 l = sub(Lp, ip);
-            float mg = mag(l);
-            l = dvs(l, mg);
+            float mg;
+            l = normalize_mag_x(l, mg);
             mg *= mg;
             const int V = (int)((vis >> j) & 1u);
             const v3 kl = xyz(s.lights[2 * j + 1]);
             const v3 ks = xyz(s.mats[3 * m]), kd = xyz(s.mats[3 * m + 1]);
             const float ndl = dot(n, l);
-            const v3 hv = normalize(add(l, v));
+            const v3 hv = normalize_x(add(l, v));
             const float coeff = fmaxf(0.0f, dot(n, hv));
             const v3 cr = mk(kd.x * fmaxf(0.0f, ndl) + ks.x * coeff, kd.y * fmaxf(0.0f, ndl) + ks.y * coeff,
                              kd.z * fmaxf(0.0f, ndl) + ks.z * coeff);
             const float fV = (float)V;
-            col.x = col.x + fV * kl.x * cr.x / mg;
-            col.y = col.y + fV * kl.y * cr.y / mg;
-            col.z = col.z + fV * kl.z * cr.z / mg;
+            const v3 cq = dvs_x(mk(fV * kl.x * cr.x, fV * kl.y * cr.y, fV * kl.z * cr.z), mg);
+            col.x = col.x + cq.x;
+            col.y = col.y + cq.y;
+            col.z = col.z + cq.z;
         }
         pb[it * 64] = make_float4(col.x, col.y, col.z, __int_as_float(m));
         const v3 dd = mul(v, -1.0f);
-        dl = normalize(add(dd, mul(n, 2.0f * __builtin_fabsf(dot(dd, n)))));
+        dl = normalize_x(add(dd, mul(n, 2.0f * __builtin_fabsf(dot(dd, n)))));
     }  // </budget>
     return fold_pb<MAXB>(s, pb, L, tail);
 }

@@ -12,14 +12,16 @@ k_persist instantiation from its assembly and multiplies them by a launch's coun
    compiled from (.loc). A line belongs to a part by the function it lies in (PARTS below) or, inside shadow_pool and
    trace_path_dfr, by the `<budget:NAME>` ... `</budget>` comments around the refill's hand-out, the ray formation, the
    list build, the closest levels' setup and the shading loop. Lines of the small vector helpers in rt_device.hpp (sub,
-   dot, dvs, rcp_ieee: inlined everywhere) inherit the part of the instruction before them.
+   dot, dvs, rcp_ieee: inlined everywhere) and of rt_exact.hpp's forms inherit the part of the instruction before them.
    A part's static count is what one pass through its code costs only as far as the code is straight-line and present
    once: the node test, the stack and the triangle tests exist once per walk kind (closest and shadow), so a step is
    priced at their sum / 2; loops inside a part (the cursor hand-out's, the face search of degenerate_ok) count once.
 2. The counters: a PRT_DEFS=-DPRT_DIAG_REFILL build under RT_FLAG_COUNTERS reports refill rounds, cursor-loop
    iterations, lanes refilled and lists built in the lane-count bins (steps_lanes_16 / 32 / 48 / 64), next to the
    wave steps. `--run` renders one batch and reads them (PRT_LIB_DIR=<the diagnostics build>); `--counters FILE` takes
-   a JSON object with wave_steps, rounds, iters, lanes, lists, tiles, levels (closest levels run per tile, summed).
+   a JSON object with wave_steps, rounds, iters, lanes, lists, tiles, levels (closest levels run per tile, summed)
+   and shade_hits (shading-loop iterations that shade a hit; absent: one per tile). The same build counts both per
+   tile and level in the histogram's slots (PRT_LEVEL_CNT, rt_kernels.hpp).
 
 usage: tools/stream_budget.py [--asm /tmp/isa/one.s] [--kernel SUBSTR] [--run [--cursor] [--scene dragon] [--frames 4]]
                               [--counters FILE]
@@ -54,14 +56,14 @@ PARTS = {
 }
 FUNC_PART = {f: p for p, fs in PARTS.items() for f in fs}
 FUNC_PART["shadow_pool"] = "walk loop"  # (its lines outside the budget marks: the pool's walk loop)
-NEUTRAL_FILE = "rt_device.hpp"          # (except hit_triangle)
+NEUTRAL_FILES = ("rt_device.hpp", "rt_exact.hpp")  # (except hit_triangle)
 FUNC_RE = re.compile(r"^(?:__device__|__global__|__host__|inline|static|void|template\b.*>\s*__device__)[^;]*?\b(\w+)\(")
 
 
 def line_parts(path):
     """line number -> part of one source file: by enclosing function, overridden by the budget marks"""
     out, fn, mark = {}, None, None
-    neutral = os.path.basename(path) == NEUTRAL_FILE
+    neutral = os.path.basename(path) in NEUTRAL_FILES
     for i, l in enumerate(open(path), 1):
         m = FUNC_RE.match(l)
         if m and not l.rstrip().endswith(";"):
@@ -163,11 +165,16 @@ def run_counters(scene, frames, cursor):
     st, li = r.stats(), r.launch_info()
     r.close()
     tiles = frames * ((W + 7) // 8) * ((H + 7) // 8)
-    # (closest levels run per tile: no counter; 4 per tile is the upper bound at 4 bounces)
+    # the diagnostics build's histogram slots (PRT_LEVEL_CNT): closest levels run, shading-loop iterations, and those
+    # of them that shade a hit, one per tile (wave) and level
+    h = st["steps_hist"]
+    levels, shade_iters, shade_hits = (sum(h[k][l][b] for l in range(4)) for k, b in ((0, 0), (1, 0), (1, 1)))
     return {"frames": frames, "wave_steps": st["wave_steps"], "shadow_wave_steps": st["shadow_wave_steps"],
             "rounds": st["steps_lanes_16"], "iters": st["steps_lanes_32"], "lanes": st["steps_lanes_48"],
             "lists": st["steps_lanes_64"], "tiles": tiles, "shadow_rays": st["shadow"],
-            "levels": 4 * tiles, "build_bits": li["build_bits"]}
+            "levels": levels, "shade_iters": shade_iters, "shade_hits": shade_hits,
+            "levels_by_level": [h[0][l][0] for l in range(4)], "shade_hits_by_level": [h[1][l][1] for l in range(4)],
+            "build_bits": li["build_bits"]}
 
 
 def main():
@@ -207,7 +214,9 @@ def main():
             ("ray formation", ctr["rounds"], g("ray formation")),
             ("list build", ctr.get("lists", 0), g("list build")),
             ("closest-level setup", ctr["levels"], g("closest-level setup") / 4.0),
-            ("shading", ctr["tiles"], g("shading"))]
+            ("shading", ctr.get("shade_hits", ctr["tiles"]), g("shading"))]
+    # (shading: the loop's body is present once and runs once per level that shades a hit; an iteration that only
+    # writes a miss colour and leaves, shade_iters - shade_hits of them, is a handful of instructions and is not priced)
     # (the cursor hand-out's loop body runs once per iteration, its frame once per round: priced together per event)
     total = sum(n * p for _, n, p in rows)
     print(f"{'part':22s} {'events':>12s} {'instr/event':>12s} {'M instr':>10s} {'share':>7s}")
