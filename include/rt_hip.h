@@ -690,6 +690,73 @@ typedef struct rt_sweep_info {
  * valid), RT_E_STATE before the first */
 int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info);
 
+/* Contact queries: per caller-supplied moving sphere the k earliest contacts with the mesh, and how many there are --
+ * rt_sweep_spheres' plural form (every triangle a sphere touches where it starts, every triangle that shares the touched
+ * edge or vertex, the sheets behind the first one, the triangles a capsule overlaps).
+ * Query i is rt_sweep_spheres' own: centre c + t d, radius r, 0 <= t <= T = fminf(t_max[i], FLT_MAX). Its candidate set
+ * is the sweep's own, in its order:
+ *   S_i = { j : toi(i, triangle j) exists and toi <= T }, ordered by (toi ascending, original index ascending),
+ * with toi exactly the sequence stated for rt_sweep_spheres above (gate, recentre, seven candidates). toi of a pair does
+ * NOT depend on the bound: T enters step 1 only as the first value of t1, t0 is made of 0 and the plane times, and steps 2
+ * and 3 read t0 alone. The bound only decides rejection (t0 <= t1, toi <= T), so a pair has one toi whatever limit a walk
+ * holds when it meets it; the plural form relies on that.
+ * S_i is empty, decided before any walk, under the sweep's rules: a non-finite c, d or r, r < 0, a NaN or negative
+ * t_max[i]. No input value is an error.
+ * Results, for max_tris in 0..RT_CONTACTS_MAX:
+ *   tri[i][0..max_tris)       the first max_tris entries of S_i (unused slots: -1)
+ *   t[i][0..max_tris)         their toi (unused slots: FLT_MAX)
+ *   point[i][0..max_tris)[3]  rt_nearest_points' P of the centre c + d*toi_j on triangle j: each contact's own contact
+ *                             point; the caller's normal is (c + d*toi_j) - P (unused slots: c's own bits)
+ *   count[i]                  min(|S_i|, max_tris), or |S_i| itself with count_all
+ * max_tris = 0 needs count_all and a count pointer: the pure count. With t_max = 1 it is the number of triangles that
+ * the capsule from c to c + d of radius r touches.
+ * With max_tris = 1 and no count_all, tri, t and point are rt_sweep_spheres' answer bit for bit. A d = 0 count is NOT
+ * promised to equal rt_nearest_tris' radius count bit for bit: the gate's rounded tlo - r can differ from D <= r*r by
+ * an ulp.
+ * RT_KERNEL_STRICT runs every sweep against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * slots in order of their gate t0, pruned at fminf(T, the max_tris-th toi found so far) -- at T alone with count_all --
+ * and answers with the same bits. A scene without a wide view (RT_ACCEL_REFERENCE) and a sweep outside
+ * rt_sweep_spheres' walk domain run the exhaustive loop under either kernel.
+ * A contacts query touches nothing a render or any other query owns. */
+#define RT_CONTACTS_MAX 16
+typedef struct rt_sphere_contacts {
+    const float* centre;  /* device, [n][3] f32: c */
+    const float* motion;  /* device, [n][3] f32: d, not normalised */
+    const float* radius;  /* device, [n] f32: r >= 0 */
+    const float* t_max;   /* device, [n] f32, nullable (NULL or +inf: no bound) */
+    int n;                /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;         /* 0..RT_CONTACTS_MAX */
+    int count_all;        /* 0 / 1 */
+    int kernel;           /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_sphere_contacts;
+typedef struct rt_contact_results { /* device pointers, all nullable: [n][max_tris], [n][max_tris],
+                                       [n][max_tris][3], [n] */
+    int* tri;
+    float* t;
+    float* point;
+    int* count;   /* required for max_tris = 0 */
+} rt_contact_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, a null centre, motion or radius with n > 0, max_tris outside 0..RT_CONTACTS_MAX,
+ * max_tris > 0 with tri, t and point all NULL, max_tris = 0 without count_all and a count pointer, count_all not 0 / 1,
+ * an unknown kernel, a negative n. */
+int rt_sweep_contacts(rt_ctx* ctx, const rt_sphere_contacts* spheres, const rt_contact_results* out);
+typedef struct rt_contacts_info {
+    long long spheres, found;             /* found: sweeps with a non-empty S_i */
+    long long tris_stored, tris_counted;  /* sums of min(|S_i|, max_tris) and of count[i] */
+    long long walked_spheres;             /* sweeps that walked the wide view */
+    long long exhaustive_spheres; /* sweeps run against every triangle: all valid ones under RT_KERNEL_STRICT or without
+                                     a wide view, and those outside the walk's domain (an invalid sweep is in neither) */
+    long long empty_spheres;      /* spheres - found */
+    long long nodes_visited;      /* wide nodes decoded, summed over the sweeps (a level popped again counts again) */
+    long long tris_tested;        /* evaluations of toi, summed over the sweeps (exhaustive: sweeps x triangles) */
+    long long stack_overflows;    /* must be 0 */
+    float kernel_ms;              /* HIP events around the query's launch */
+} rt_contacts_info;
+/* counters of the last contacts query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_contacts_info(rt_ctx* ctx, rt_contacts_info* info);
+
 /* Cut queries: per caller-supplied triangle the mesh triangles it crosses, how many, and the segment along which each
  * pair crosses -- the query for the shape the scene itself is made of (mesh against mesh: the faces of a part, a tool
  * or a cloth that cross the uploaded mesh; cutting: where a sheet crosses the surface, as segments that chain into

@@ -40,6 +40,7 @@
 #include "rt_neighbours.hpp"
 #include "rt_overlap.hpp"
 #include "rt_sweep.hpp"
+#include "rt_contacts.hpp"
 #include "rt_cut.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
@@ -269,6 +270,12 @@ struct rt_ctx {
     hipEvent_t w_ev0 = nullptr, w_ev1 = nullptr;
     bool sweeps_run = false, w_launched = false;
     std::unordered_map<const void*, int> w_resident;  // resident workgroups of each k_sweep instantiation
+    // contact queries (rt_sweep_contacts, rt_contacts.hpp): their own again ([rtd::CT_NCOUNT] counters, then the chunk
+    // counter); they share d_ref_inv with the neighbour queries
+    unsigned long long* d_ctq = nullptr;
+    hipEvent_t c_ev0 = nullptr, c_ev1 = nullptr;
+    bool contacts_run = false, c_launched = false;
+    std::unordered_map<const void*, int> c_resident;  // resident workgroups of each k_contacts instantiation
     // cut queries (rt_cut_triangles, rt_cut.hpp): their own again ([rtd::X_NCOUNT] counters, then the chunk counter)
     unsigned long long* d_cutq = nullptr;
     hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;
@@ -3617,6 +3624,119 @@ extern "C" int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- contact queries (rt_contacts.hpp)
+namespace {
+using CFn = void (*)(rtd::CArgs);
+// the smallest list capacity that holds max_tris (0: the counting build)
+CFn contacts_kernel(int max_tris, bool strict) {
+    using rtd::k_contacts;
+    if (max_tris == 0) return strict ? k_contacts<0, true> : k_contacts<0, false>;
+    if (max_tris <= 4) return strict ? k_contacts<4, true> : k_contacts<4, false>;
+    if (max_tris <= 8) return strict ? k_contacts<8, true> : k_contacts<8, false>;
+    return strict ? k_contacts<16, true> : k_contacts<16, false>;
+}
+}  // namespace
+
+extern "C" int rt_sweep_contacts(rt_ctx* ctx, const rt_sphere_contacts* r, const rt_contact_results* out) {
+    static_assert(RT_CONTACTS_MAX == rtd::CONTACTS_MAX, "rt_hip.h and rt_contacts.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_sweep_contacts: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_sweep_contacts: null spheres / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_sweep_contacts: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_sweep_contacts: negative sphere count");
+    if (r->max_tris < 0 || r->max_tris > RT_CONTACTS_MAX) return arg_err(ctx, "rt_sweep_contacts: max_tris must be 0..16");
+    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_sweep_contacts: count_all must be 0 or 1");
+    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_sweep_contacts: max_tris = 0 needs count_all");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->centre || !r->motion || !r->radius))
+        return arg_err(ctx, "rt_sweep_contacts: null centre / motion / radius");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->t && !out->point)
+        return arg_err(ctx, "rt_sweep_contacts: max_tris > 0 needs a tri, a t or a point output");
+    if (r->n > 0 && r->max_tris == 0 && !out->count)
+        return arg_err(ctx, "rt_sweep_contacts: a counting query needs a count output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::CT_NCOUNT + 1);
+    if (!ctx->d_ctq) HIPC(hipMalloc((void**)&ctx->d_ctq, cbytes));
+    if (!ctx->c_ev0) HIPC(hipEventCreate(&ctx->c_ev0));
+    if (!ctx->c_ev1) HIPC(hipEventCreate(&ctx->c_ev1));
+    HIPC(hipMemsetAsync(ctx->d_ctq, 0, cbytes, ctx->stream));
+    ctx->contacts_run = true;
+    ctx->c_launched = false;
+    if (r->n == 0) return RT_OK;
+    const bool want_p = r->max_tris > 0 && out->point;
+    if (want_p && !ctx->d_ref_inv) {  // original index -> the reference tree's record (rt_neighbours.hpp ref_inv)
+        const int nt = ctx->n_tris;
+        HIPC(hipMalloc((void**)&ctx->d_ref_inv, sizeof(int) * (size_t)std::max(nt, 1)));
+        HIPC(hipMemsetAsync(ctx->d_ref_inv, 0, sizeof(int) * (size_t)std::max(nt, 1), ctx->stream));
+        if (nt > 0) {
+            rtd::k_invert_orig<<<(nt + 255) / 256, 256, 0, ctx->stream>>>(ctx->ref.orig, nt, ctx->d_ref_inv);
+            HIPC(hipGetLastError());
+        }
+    }
+    rtd::CArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.centre = r->centre;
+    A.motion = r->motion;
+    A.radius = r->radius;
+    A.t_max = r->t_max;
+    A.tri = r->max_tris > 0 ? out->tri : nullptr;
+    A.t = r->max_tris > 0 ? out->t : nullptr;
+    A.out = want_p ? out->point : nullptr;
+    A.count = out->count;
+    A.ref_inv = ctx->d_ref_inv;
+    A.counters = ctx->d_ctq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_ctq + rtd::CT_NCOUNT);
+    A.n = r->n;
+    A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::sweep_domain
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    const CFn k = contacts_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->c_resident.find((const void*)k);
+    if (res == ctx->c_resident.end()) res = ctx->c_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->c_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->c_ev1, ctx->stream));
+    ctx->c_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_contacts_info(rt_ctx* ctx, rt_contacts_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->contacts_run) {
+        ctx->err = "rt_get_contacts_info: no contacts query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::CT_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_ctq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->spheres = (long long)c[rtd::CT_SPHERES];
+    info->found = (long long)c[rtd::CT_FOUND];
+    info->tris_stored = (long long)c[rtd::CT_STORED];
+    info->tris_counted = (long long)c[rtd::CT_COUNTED];
+    info->walked_spheres = (long long)c[rtd::CT_WALKED];
+    info->exhaustive_spheres = (long long)c[rtd::CT_EXH];
+    info->empty_spheres = (long long)c[rtd::CT_EMPTY];
+    info->nodes_visited = (long long)c[rtd::CT_NODES];
+    info->tris_tested = (long long)c[rtd::CT_TRIS];
+    info->stack_overflows = (long long)c[rtd::CT_ERR];
+    if (ctx->c_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->c_ev0, ctx->c_ev1));
+    if (c[rtd::CT_ERR]) {
+        ctx->err = "rt_get_contacts_info: the query's traversal stack overflowed " + std::to_string(c[rtd::CT_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 // ---------------------------------------------------------------- cut queries (rt_cut.hpp)
 namespace {
 using XFn = void (*)(rtd::XArgs);
@@ -4602,6 +4722,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_swq) (void)hipFree(ctx->d_swq);
     if (ctx->w_ev0) (void)hipEventDestroy(ctx->w_ev0);
     if (ctx->w_ev1) (void)hipEventDestroy(ctx->w_ev1);
+    if (ctx->d_ctq) (void)hipFree(ctx->d_ctq);
+    if (ctx->c_ev0) (void)hipEventDestroy(ctx->c_ev0);
+    if (ctx->c_ev1) (void)hipEventDestroy(ctx->c_ev1);
     if (ctx->d_cutq) (void)hipFree(ctx->d_cutq);
     if (ctx->x_ev0) (void)hipEventDestroy(ctx->x_ev0);
     if (ctx->x_ev1) (void)hipEventDestroy(ctx->x_ev1);

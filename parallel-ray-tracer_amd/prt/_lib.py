@@ -230,6 +230,28 @@ class SweepInfo(ctypes.Structure):  # rt_sweep_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+CONTACTS_MAX = 16  # RT_CONTACTS_MAX
+
+
+class SphereContacts(ctypes.Structure):  # rt_sphere_contacts
+    _fields_ = [("centre", ctypes.c_void_p), ("motion", ctypes.c_void_p), ("radius", ctypes.c_void_p),
+                ("t_max", ctypes.c_void_p), ("n", ctypes.c_int), ("max_tris", ctypes.c_int),
+                ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class ContactResults(ctypes.Structure):  # rt_contact_results
+    _fields_ = [("tri", ctypes.c_void_p), ("t", ctypes.c_void_p), ("point", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
+class ContactsInfo(ctypes.Structure):  # rt_contacts_info
+    _fields_ = [("spheres", ctypes.c_longlong), ("found", ctypes.c_longlong), ("tris_stored", ctypes.c_longlong),
+                ("tris_counted", ctypes.c_longlong), ("walked_spheres", ctypes.c_longlong),
+                ("exhaustive_spheres", ctypes.c_longlong), ("empty_spheres", ctypes.c_longlong),
+                ("nodes_visited", ctypes.c_longlong), ("tris_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 CUTS_MAX = 16  # RT_CUTS_MAX
 
 
@@ -380,7 +402,9 @@ def hip():
         L.rt_get_overlaps_info.argtypes = [ctypes.c_void_p, P(OverlapsInfo)]
         L.rt_sweep_spheres.argtypes = [ctypes.c_void_p, P(Spheres), P(SweepResults)]
         L.rt_get_sweep_info.argtypes = [ctypes.c_void_p, P(SweepInfo)]
-        L.rt_cut_triangles.argtypes = [ctypes.c_void_p, P(Tris), P(CutResults)]
+        L.rt_sweep_contacts.argtypes = [ctypes.c_void_p, P(SphereContacts), P(ContactResults)]
+        L.rt_get_contacts_info.argtypes = [ctypes.c_void_p, P(ContactsInfo)]
+        L.rt_cut_triangles.argtypes =[ctypes.c_void_p, P(Tris), P(CutResults)]
         L.rt_get_cuts_info.argtypes = [ctypes.c_void_p, P(CutsInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]

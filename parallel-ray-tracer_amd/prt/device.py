@@ -662,20 +662,12 @@ class Renderer:
         self._chk(_L.rt_get_overlaps_info(self._ctx, ctypes.byref(i)), "rt_get_overlaps_info")
         return {f: getattr(i, f) for f, _ in _lib.OverlapsInfo._fields_}
 
-    def sweep(self, centres, motions, radius, t_max=None, kernel="fast", tri=None, t=None, point=None):
-        """rt_sweep_spheres: per moving sphere -- centre c + t d at time t, radius r -- its first contact with the scene:
-        the first triangle by (toi, original triangle index), whatever the BVH (include/rt_hip.h states toi) -> (tri [n]
-        int32, -1 when nothing is touched within the bound; t [n] float32 = toi, FLT_MAX then; point [n, 3] float32 =
-        the contact point, the centre's own bits then). The caller's normal is (c + t d) - point. centres, motions:
-        [n, 3] float32 contiguous tensors on this device (or raw pointers: centres=(pointer, n), motions=pointer, with
-        radius a raw pointer too); motions are not normalised, and d = 0 asks "does it touch now". radius: a float, or
-        an [n] float32 tensor (r >= 0; 0 is a thin sweep). t_max: optional [n] float32 tensor of bounds on t (+inf: none;
-        0: touching now; NaN or negative: nothing). kernel="strict" runs every sweep against every triangle (the
-        checker), "fast" / "auto" walks the full wide view with the same bits. tri / t / point: optional outputs
-        (allocated when not given). Asynchronous on the renderer's stream: sync() or sweep_info() before the results
-        are read on another stream."""
+    @staticmethod
+    def _spheres(centres, motions, radius, t_max):
+        """the sweep queries' input checks -> (n, centre, motion and radius pointers when they were given raw, else
+        None): centres, motions [n, 3] tensors with radius a float or an [n] tensor, or raw pointers given as
+        centres=(pointer, n), motions=pointer, radius=pointer; t_max an [n] tensor, a raw pointer or None"""
         import torch
-        f32, i32 = (torch.float32,), (torch.int32,)
         if isinstance(centres, tuple):
             pc, n = centres
             if (not isinstance(pc, int) or not isinstance(n, int) or n < 0 or not isinstance(motions, int) or
@@ -683,6 +675,7 @@ class Renderer:
                 raise RtError("spheres: raw pointers are given as centres=(pointer, n), motions=pointer, radius=pointer")
             pd, pr = motions, radius
         else:
+            pc = pd = pr = None
             for x, what in ((centres, "centres"), (motions, "motions")):
                 if not isinstance(x, torch.Tensor):
                     raise RtError(f"{what}: expected a torch tensor or raw pointers, got {type(x).__name__}")
@@ -702,6 +695,23 @@ class Renderer:
             raise RtError(f"t_max: expected a torch tensor, got {type(t_max).__name__}")
         if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
             raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
+        return n, pc, pd, pr
+
+    def sweep(self, centres, motions, radius, t_max=None, kernel="fast", tri=None, t=None, point=None):
+        """rt_sweep_spheres: per moving sphere -- centre c + t d at time t, radius r -- its first contact with the scene:
+        the first triangle by (toi, original triangle index), whatever the BVH (include/rt_hip.h states toi) -> (tri [n]
+        int32, -1 when nothing is touched within the bound; t [n] float32 = toi, FLT_MAX then; point [n, 3] float32 =
+        the contact point, the centre's own bits then). The caller's normal is (c + t d) - point. centres, motions:
+        [n, 3] float32 contiguous tensors on this device (or raw pointers: centres=(pointer, n), motions=pointer, with
+        radius a raw pointer too); motions are not normalised, and d = 0 asks "does it touch now". radius: a float, or
+        an [n] float32 tensor (r >= 0; 0 is a thin sweep). t_max: optional [n] float32 tensor of bounds on t (+inf: none;
+        0: touching now; NaN or negative: nothing). kernel="strict" runs every sweep against every triangle (the
+        checker), "fast" / "auto" walks the full wide view with the same bits. tri / t / point: optional outputs
+        (allocated when not given). Asynchronous on the renderer's stream: sync() or sweep_info() before the results
+        are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        n, pc, pd, pr = self._spheres(centres, motions, radius, t_max)
         if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
             raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
         if not isinstance(centres, tuple):
@@ -736,6 +746,66 @@ class Renderer:
         i = _lib.SweepInfo()
         self._chk(_L.rt_get_sweep_info(self._ctx, ctypes.byref(i)), "rt_get_sweep_info")
         return {f: getattr(i, f) for f, _ in _lib.SweepInfo._fields_}
+
+    def sweep_contacts(self, centres, motions, radius, k=8, t_max=None, count_all=False, points_out=False,
+                       kernel="auto", tri=None, t=None, count=None, point=None):
+        """rt_sweep_contacts: per moving sphere its k earliest contacts with the scene -- the first k by (toi, original
+        triangle index) among the triangles with toi <= t_max, sweep's own set and order (include/rt_hip.h) -> (tri
+        [n, k] int32, -1 in unused slots; t [n, k] float32 = each contact's toi, FLT_MAX in unused slots; count [n] int32
+        = min(contacts within the bound, k), or every contact within the bound with count_all=True, when the walk prunes
+        at the bound only), plus point [n, k, 3] float32 (each contact's own contact point, at the centre c + toi_j d;
+        the centre's own bits in unused slots) with points_out=True or a `point` output. k: 0..16; 0 with
+        count_all=True is a pure count (tri and t come back empty) -- with t_max = 1 the number of triangles the capsule
+        from c to c + d touches. With k = 1 the answer is sweep's, bit for bit. centres, motions, radius, t_max and
+        kernel as sweep takes them; without a bound count_all counts every triangle the sphere ever touches.
+        tri / t / count / point: optional outputs (allocated when not given). Asynchronous on the renderer's stream:
+        sync() or contacts_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.CONTACTS_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.CONTACTS_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        n, pc, pd, pr = self._spheres(centres, motions, radius, t_max)
+        if isinstance(point, torch.Tensor) and (point.dim() != 3 or tuple(point.shape[1:]) != (k, 3)):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, {k}, 3]")
+        if not isinstance(centres, tuple):
+            pc = _ptr(centres, "centres", 3 * n, f32, self.device)
+            pd = _ptr(motions, "motions", 3 * n, f32, self.device)
+        pm = _ptr(t_max, "t_max", n, f32, self.device)
+        for x, what, m, dt in ((tri, "tri", n * k, i32), (t, "t", n * k, f32), (count, "count", n, i32),
+                               (point, "point", 3 * n * k, f32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if not isinstance(centres, tuple):
+            if not isinstance(radius, torch.Tensor):
+                radius = torch.full((n,), float(radius), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(self.device).synchronize()  # (the fill is torch's work, the query runs on ours)
+            pr = _ptr(radius, "radius", n, f32, self.device)
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        if point is None and points_out:
+            point = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        res = _lib.ContactResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                                  _ptr(t, "t", n * k, f32, self.device) if k else None,
+                                  _ptr(point, "point", 3 * n * k, f32, self.device) if k else None,
+                                  _ptr(count, "count", n, i32, self.device))
+        q = _lib.SphereContacts(pc, pd, pr, pm, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_sweep_contacts(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_sweep_contacts")
+        self._contacts_keep = radius  # (a radius tensor made here lives until the next query: the launch is asynchronous)
+        return (tri, t, count) if point is None else (tri, t, count, point)
+
+    def contacts_info(self):
+        """rt_get_contacts_info: the last contacts query's counters (spheres, found, tris_stored, tris_counted,
+        walked_spheres, exhaustive_spheres, empty_spheres, nodes_visited, tris_tested) and kernel_ms; synchronises;
+        raises when the query overflowed its stack"""
+        i = _lib.ContactsInfo()
+        self._chk(_L.rt_get_contacts_info(self._ctx, ctypes.byref(i)), "rt_get_contacts_info")
+        return {f: getattr(i, f) for f, _ in _lib.ContactsInfo._fields_}
 
     def overlaps_csr(self, lo, hi, kernel="auto"):
         """every box's full S_i, in index order -> (offsets [n + 1] int32, tris [offsets[n]] int32): box i's triangles

@@ -16,7 +16,8 @@ closest-hit query (hits_mode below), --mode nearest rt_nearest_p
 --mode neighbours rt_nearest_tris beside rt_nearest_points (neighbours_mode below), --mode overlap
 rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below), --mode sweep
 rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below), --mode cuts
-rt_cut_triangles beside rt_overlap_boxes on the query triangles' corner boxes (cuts_mode below).
+rt_cut_triangles beside rt_overlap_boxes on the query triangles' corner boxes (cuts_mode below), --mode
+contacts rt_sweep_contacts beside rt_sweep_spheres on the same sweeps (contacts_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
@@ -24,7 +25,8 @@ usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --h
        python tools/query_bench.py --mode neighbours [--runs 7] [--out profiles/neighbours_bench_<md5>.jsonl]
        python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]
        python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode cuts [--runs 5] [--out profiles/cuts_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode cuts [--runs 5] [--out profiles/cuts_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode contacts [--runs 5] [--out profiles/contacts_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -41,7 +43,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts"],
+    ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts",
+                                       "contacts"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
@@ -49,9 +52,10 @@ def main():
                          "neighbours: rt_nearest_tris beside rt_nearest_points (neighbours_mode); "
                          "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode); "
                          "sweep: rt_sweep_spheres beside the closest-hit query (sweep_mode); "
-                         "cuts: rt_cut_triangles beside rt_overlap_boxes on the corner boxes (cuts_mode)")
+                         "cuts: rt_cut_triangles beside rt_overlap_boxes on the corner boxes (cuts_mode); "
+                         "contacts: rt_sweep_contacts beside rt_sweep_spheres (contacts_mode)")
     ap.add_argument("--out", default=None,
-                    help="nearest, neighbours, overlap, sweep, cuts: also append the raw lines to this file")
+                    help="nearest, neighbours, overlap, sweep, cuts, contacts: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
     a = ap.parse_args()
     import numpy as np
@@ -73,6 +77,8 @@ def main():
         return sweep_mode(a, md5)
     if a.mode == "cuts":
         return cuts_mode(a, md5)
+    if a.mode == "contacts":
+        return contacts_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -764,6 +770,94 @@ def cuts_mode(a, md5):
             if total > CSR_CAP:
                 print(json.dumps({"scene": name, "set": label, "arm": "cut_csr", "skipped": "set_entries above the cap",
                                   "set_entries": total, "cap": CSR_CAP}), flush=True)
+        r.close()
+    if out:
+        out.close()
+
+
+def contacts_mode(a, md5):
+    """--mode contacts: per scene, rt_sweep_contacts on sweep_mode's W x H sweeps (the camera's primary
+    rays, and the unit-length bounce rays from the primary hit points) at radii of 0, 0.1 %, 1 % and 5 % of the scene's
+    extent: the lists of k = 1, 4, 8 and 16 contacts (tri, t and count; no points), and the pure count with t_max = 1
+    (the capsule count: the triangles that the capsule from c to c + d touches), beside rt_sweep_spheres on the same
+    sweeps, and the exhaustive kernel's k = 16 on 4,096 of the sweeps. One untimed round first; then --runs rounds with
+    the arms interleaved; kernel_ms from the HIP events around each launch. One JSON line per arm: median / min / max
+    ms, the ratio of the medians to rt_sweep_spheres', the per-sweep ratio to the exhaustive kernel, nodes_visited and
+    tris_tested (toi evaluations) per sweep, the counters, and whether the fast kernel equals the exhaustive one on the
+    4,096 sweeps (every output's bits, points included)."""
+    import numpy as np
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        o, d, g, _ = point_sets(r, s, W, H)
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        bo = (o + d * torch.where(hit >= 0, t, torch.ones_like(t))[:, None]).contiguous()
+        bd = torch.randn(n, 3, generator=g)
+        bd = (bd / bd.norm(dim=1, keepdim=True)).cuda().contiguous()
+        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+        ext = float((v.max(0) - v.min(0)).max())
+        one = torch.ones(n, dtype=torch.float32, device="cuda")
+        for label, so, sd in (("primary", o, d), ("bounce", bo, bd)):
+            pick = torch.randperm(n, generator=g)[:NS].cuda()
+            po, pd = so[pick].contiguous(), sd[pick].contiguous()
+            torch.cuda.synchronize()
+            for pct in (0.0, 0.1, 1.0, 5.0):
+                rad = torch.full((n,), ext * pct / 100, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+
+                def sweep():
+                    res = r.sweep(so, sd, rad, kernel="fast")
+                    return r.sweep_info(), res, n
+
+                def contacts(k, c=so, m=sd, kernel="fast", capsule=False, points=False):
+                    res = r.sweep_contacts(c, m, rad[:len(c)], k=k, t_max=one[:len(c)] if capsule else None,
+                                           count_all=k == 0, points_out=points, kernel=kernel)
+                    return r.contacts_info(), res, len(c)
+
+                arms = [("sweep_spheres", sweep)]
+                arms += [(f"contacts_k{k}", lambda k=k: contacts(k)) for k in (1, 4, 8, 16)]
+                arms += [("capsule_count", lambda: contacts(0, capsule=True)),
+                         ("contacts_k16_exhaustive_4096", lambda: contacts(16, po, pd, "strict"))]
+                same = {}
+                for key, k, capsule in [(f"contacts_k{k}", k, False) for k in (1, 4, 8, 16)] + [("capsule_count", 0,
+                                                                                                   True)]:
+                    x = contacts(k, po, pd, capsule=capsule, points=k > 0)[1]
+                    y = contacts(k, po, pd, "strict", capsule=capsule, points=k > 0)[1]
+                    same[key] = all(bool((p.view(torch.int32) == q.view(torch.int32)).all()) for p, q in zip(x, y))
+                for _, fn in arms:  # the untimed round
+                    fn()
+                ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+                for _ in range(a.runs):
+                    for k, fn in arms:
+                        last[k], _, cnt[k] = fn()
+                        ms[k].append(last[k]["kernel_ms"])
+                med = {k: statistics.median(ms[k]) for k, _ in arms}
+                for k, _ in arms:
+                    info = last[k]
+                    line = {"scene": name, "set": label, "radius_pct": pct, "arm": k, "sweeps": cnt[k],
+                            "extent": round(ext, 4), "msweeps_s": round(cnt[k] / med[k] / 1e3, 2),
+                            "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                            "kernel_ms_max": round(max(ms[k]), 4),
+                            "ratio_to_sweep_spheres": round((med[k] / cnt[k]) / (med["sweep_spheres"] / n), 3),
+                            "per_sweep_ratio_to_exhaustive": round((med[k] / cnt[k]) /
+                                                                   (med["contacts_k16_exhaustive_4096"] / NS), 6),
+                            "runs": a.runs, "sample_equals_exhaustive": same.get(k),
+                            "nodes_visited_per_sweep": round(info["nodes_visited"] / cnt[k], 2),
+                            "tris_tested_per_sweep": round(info["tris_tested"] / cnt[k], 2),
+                            "info": {x: w for x, w in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                    if "tris_counted" in info:
+                        line["contacts_per_sweep"] = round(info["tris_counted"] / cnt[k], 3)
+                    print(json.dumps(line), flush=True)
+                    if out:
+                        out.write(json.dumps(line) + "\n")
+                        out.flush()
         r.close()
     if out:
         out.close()
