@@ -837,6 +837,92 @@ typedef struct rt_cuts_info {
  * valid), RT_E_STATE before the first */
 int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info);
 
+/* Clearance queries: per caller-supplied triangle the nearest mesh triangle, the squared distance to it and the pair of
+ * points where the two come closest -- rt_cut_triangles' distance form, as rt_nearest_points is a point's (the clearance
+ * of a placed part against the scene, tolerance and clash margins, proximity pairs for cloth and contact solvers, the
+ * gap between a tool and a surface: what is asked as soon as rt_cut_triangles answers "nothing").
+ * Query i is a triangle q0, q1, q2 with an optional bound max_dist2[i]. Its candidate set is
+ *   S_i = { j : D(q, triangle j) <= min(max_dist2[i], FLT_MAX) }, ordered by (D ascending, original index ascending),
+ * and the answer is its first element: a total order, so the answer depends on no BVH.
+ * Every operation is one float32 operation and nothing is contracted into an FMA. dot(u, v) = u.x*v.x + u.y*v.y + u.z*v.z
+ * left to right; clamp01(x) = fminf(fmaxf(x, 0), 1); fminf / fmaxf with C semantics (a NaN operand loses); IEEE
+ * division; a comparison with a NaN operand is false.
+ * Records and boxes. The mesh triangle is its record a = v0, e1 = fl(v1 - v0), e2 = fl(v2 - v0), with corners a,
+ * b = fl(a + e1), c = fl(a + e2) and corner box [tlo, thi] (rt_overlap_boxes' step 1). The query is made a record the
+ * same way: f1 = fl(q1 - q0), f2 = fl(q2 - q0), qb = fl(q0 + f1), qc = fl(q0 + f2). The query box [qlo, qhi] is the
+ * componentwise fminf / fmaxf over the FIVE points q0, q1, q2, qb, qc (folded in that order): it holds the raw corners
+ * that rt_cut_triangles' X gates on and the record corners that the candidates use.
+ * D of a pair is the least of fifteen candidates, offered in this order; a candidate replaces the pair's best only when
+ * its D is strictly smaller:
+ *   0..2    the query corners q0, qb, qc against the mesh record, by rt_nearest_points' own D and P: the pair of points
+ *           is (corner, P);
+ *   3..5    the mesh corners a, b, c against the query record (q0, f1, f2), by the same function: the pair is
+ *           (P, corner);
+ *   6..14   the nine edge pairs, query edge major: candidate 6 + 3*i + j is query edge i of (q0, f1), (q0, f2),
+ *           (qb, fl(f2 - f1)) against mesh edge j of (a, e1), (a, e2), (b, fl(e2 - e1)). An edge pair (p1, d1), (p2, d2):
+ *             r = p1 - p2;  A = dot(d1, d1);  E = dot(d2, d2);  f = dot(d2, r);  c = dot(d1, r);  B = dot(d1, d2)
+ *             den = A*E - B*B
+ *             s = den > 0 ? clamp01((B*f - c*E) / den) : 0
+ *             t = (B*s + f) / E
+ *             if (t < 0) s = clamp01(-c / A); else if (t > 1) s = clamp01((B - c) / A)
+ *             t = clamp01(t)
+ *             c1 = p1 + d1*s;  c2 = p2 + d2*t
+ *             c1 = fminf(fmaxf(c1, qlo), qhi);  c2 = fminf(fmaxf(c2, tlo), thi)                       per component
+ *             df = c1 - c2;  D = dot(df, df);  the pair is (c1, c2)
+ * The crossing. After the fifteen, if rt_cut_triangles' X(q0, q1, q2; triangle) holds -- that test unchanged, on the
+ * raw corners --, then D = 0 and both points are the cut segment's first end s0.
+ * Every candidate's two points lie in [qlo, qhi] and [tlo, thi], which is what lets the walk prune with no tuned margin
+ * (DESIGN.md §3y); every D is >= +0, and the fifteen candidates' points are finite for finite triangles.
+ * Results: tri[i] = the original triangle index, d2[i] = D, on_query[i] and on_mesh[i] = the pair of points, kind[i] =
+ * 0..14 for the winning candidate and 15 for a crossing. The empty set gives -1, FLT_MAX, q0's own bits twice and -1;
+ * it is empty when any of the nine numbers is non-finite (decided before any walk), when max_dist2[i] is NaN or
+ * negative, or when nothing lies within the bound (0 is a valid bound: what touches). max_dist2 NULL or +inf: no bound.
+ * No input value is an error.
+ * Documented, not fixed:
+ *   - A query of zero area is valid and is answered by the fifteen candidates alone: X excludes it, as
+ *     rt_cut_triangles does. One with q1 == q2 is a segment, one with all three corners equal a point. A needle that
+ *     pierces a triangle's interior therefore reports the distance to that triangle's boundary, not 0. Segments belong
+ *     to rt_sweep_spheres with r = 0 and t_max = 1, points to rt_nearest_points.
+ *   - For a point query D is not promised to equal rt_nearest_points' bit for bit: an edge candidate may round an ulp
+ *     lower.
+ * RT_KERNEL_STRICT tests every query against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * boxes ordered and pruned by their distance to the query box, and answers with the same bits; a scene without a wide
+ * view (RT_ACCEL_REFERENCE) runs the exhaustive loop under either kernel.
+ * A clearance query touches nothing a render or any other query owns. */
+typedef struct rt_clear_tris {
+    const float* tris;      /* device, [n][3][3] f32: q0, q1, q2 of every query */
+    const float* max_dist2; /* device, [n] f32, nullable */
+    int n;                  /* >= 0; 0 is RT_OK and launches nothing */
+    int kernel;             /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_clear_tris;
+typedef struct rt_clearance_results { /* device pointers, all nullable, at least one non-null when n > 0 */
+    int* tri;        /* [n] */
+    float* d2;       /* [n] */
+    float* on_query; /* [n][3] */
+    float* on_mesh;  /* [n][3] */
+    int* kind;       /* [n] */
+} rt_clearance_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null tris with n > 0, all five outputs NULL with n > 0, an unknown kernel, a negative n. */
+int rt_clearance_triangles(rt_ctx* ctx, const rt_clear_tris* tris, const rt_clearance_results* out);
+typedef struct rt_clearance_info {
+    long long triangles, found; /* found: query triangles with a non-empty S_i */
+    long long walked;           /* query triangles that walked the wide view */
+    long long exhaustive;       /* query triangles tested against every triangle: all valid ones under RT_KERNEL_STRICT
+                                   or without a wide view (an invalid one is in neither) */
+    long long empty;            /* triangles - found */
+    long long nodes_visited;    /* wide nodes decoded, summed over the queries (a level popped again counts again) */
+    long long pairs_gated;      /* the walk: triangles of a kept leaf slot skipped because the bound of their own corner
+                                   box exceeded the limit, or equalled the best D at a higher index (pure pruning; 0 in
+                                   the exhaustive loop) */
+    long long pairs_tested;     /* evaluations of D, summed over the queries (exhaustive: queries x triangles) */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_clearance_info;
+/* counters of the last clearance query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -42,6 +42,7 @@
 #include "rt_sweep.hpp"
 #include "rt_contacts.hpp"
 #include "rt_cut.hpp"
+#include "rt_clearance.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -281,6 +282,12 @@ struct rt_ctx {
     hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;
     bool cuts_run = false, x_launched = false;
     std::unordered_map<const void*, int> x_resident;  // resident workgroups of each k_cut instantiation
+    // clearance queries (rt_clearance_triangles, rt_clearance.hpp): their own again ([rtd::CL_NCOUNT] counters, then the
+    // chunk counter)
+    unsigned long long* d_clq = nullptr;
+    hipEvent_t l_ev0 = nullptr, l_ev1 = nullptr;
+    bool clearance_run = false, l_launched = false;
+    std::unordered_map<const void*, int> l_resident;  // resident workgroups of each k_clearance instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -3839,6 +3846,85 @@ extern "C" int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- clearance queries (rt_clearance.hpp)
+extern "C" int rt_clearance_triangles(rt_ctx* ctx, const rt_clear_tris* r, const rt_clearance_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (!ctx->has_scene) {
+        ctx->err = "rt_clearance_triangles: no scene uploaded";
+        return RT_E_STATE;
+    }
+    if (!r || !out) return arg_err(ctx, "rt_clearance_triangles: null tris / results");
+    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST)
+        return arg_err(ctx, "rt_clearance_triangles: bad kernel");
+    if (r->n < 0) return arg_err(ctx, "rt_clearance_triangles: negative triangle count");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && !r->tris) return arg_err(ctx, "rt_clearance_triangles: null tris");
+    if (r->n > 0 && !out->tri && !out->d2 && !out->on_query && !out->on_mesh && !out->kind)
+        return arg_err(ctx, "rt_clearance_triangles: needs a tri, a d2, an on_query, an on_mesh or a kind output");
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (rtd::CL_NCOUNT + 1);
+    if (!ctx->d_clq) HIPC(hipMalloc((void**)&ctx->d_clq, cbytes));
+    if (!ctx->l_ev0) HIPC(hipEventCreate(&ctx->l_ev0));
+    if (!ctx->l_ev1) HIPC(hipEventCreate(&ctx->l_ev1));
+    HIPC(hipMemsetAsync(ctx->d_clq, 0, cbytes, ctx->stream));
+    ctx->clearance_run = true;
+    ctx->l_launched = false;
+    if (r->n == 0) return RT_OK;
+    rtd::CLArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.tris = r->tris;
+    A.max_dist2 = r->max_dist2;
+    A.tri = out->tri;
+    A.d2 = out->d2;
+    A.on_query = out->on_query;
+    A.on_mesh = out->on_mesh;
+    A.kind = out->kind;
+    A.counters = ctx->d_clq;
+    A.work = reinterpret_cast<unsigned int*>(ctx->d_clq + rtd::CL_NCOUNT);
+    A.n = r->n;
+    void (*k)(rtd::CLArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_clearance<true> : rtd::k_clearance<false>;
+    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
+    auto res = ctx->l_resident.find((const void*)k);
+    if (res == ctx->l_resident.end()) res = ctx->l_resident.emplace((const void*)k, resident(k, ctx->device)).first;
+    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
+    HIPC(hipEventRecord(ctx->l_ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->l_ev1, ctx->stream));
+    ctx->l_launched = true;
+    return RT_OK;
+}
+
+extern "C" int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->clearance_run) {
+        ctx->err = "rt_get_clearance_info: no clearance query run";
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    unsigned long long c[rtd::CL_NCOUNT];
+    HIPC(hipMemcpy(c, ctx->d_clq, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    info->triangles = (long long)c[rtd::CL_TRIS];
+    info->found = (long long)c[rtd::CL_FOUND];
+    info->walked = (long long)c[rtd::CL_WALKED];
+    info->exhaustive = (long long)c[rtd::CL_EXH];
+    info->empty = (long long)c[rtd::CL_EMPTY];
+    info->nodes_visited = (long long)c[rtd::CL_NODES];
+    info->pairs_gated = (long long)c[rtd::CL_GATED];
+    info->pairs_tested = (long long)c[rtd::CL_PAIRS];
+    info->stack_overflows = (long long)c[rtd::CL_ERR];
+    if (ctx->l_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->l_ev0, ctx->l_ev1));
+    if (c[rtd::CL_ERR]) {
+        ctx->err = "rt_get_clearance_info: the query's traversal stack overflowed " + std::to_string(c[rtd::CL_ERR]) +
+                   " times (wide view deeper than the walk's stack): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
 namespace {
 int comm_settle_ctx(rt_ctx* ctx, const char* who);  // (below, with the communicators)
 // Waits for the context stream; with a render behind it, reads that render's error counter (rtd::C_ERR: a traversal
@@ -4728,6 +4814,9 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
     if (ctx->d_cutq) (void)hipFree(ctx->d_cutq);
     if (ctx->x_ev0) (void)hipEventDestroy(ctx->x_ev0);
     if (ctx->x_ev1) (void)hipEventDestroy(ctx->x_ev1);
+    if (ctx->d_clq) (void)hipFree(ctx->d_clq);
+    if (ctx->l_ev0) (void)hipEventDestroy(ctx->l_ev0);
+    if (ctx->l_ev1) (void)hipEventDestroy(ctx->l_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

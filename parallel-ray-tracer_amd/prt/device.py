@@ -931,6 +931,59 @@ class Renderer:
         key, order = torch.sort(row * n_tris + idx.to(torch.int64))  # (query-major, index ascending within each)
         return offsets, (key - row * n_tris).to(torch.int32), seg[order] if segments else None
 
+    def clearance(self, tris, max_dist2=None, kernel="auto", kind=None, tri=None, d2=None, on_query=None, on_mesh=None):
+        """rt_clearance_triangles: per caller-supplied triangle q0, q1, q2 the nearest triangle of the scene, the squared
+        distance to it and the two points where the pair comes closest -- the first triangle by (D, original triangle
+        index), whatever the BVH (include/rt_hip.h states D: three corner, three mesh-corner and nine edge-pair
+        candidates, and D = 0 where cuts' X holds) -> (tri [n] int32, -1 when nothing lies within the bound; d2 [n]
+        float32, FLT_MAX then; on_query [n, 3] and on_mesh [n, 3] float32, q0's own bits then). tris: an [n, 3, 3]
+        float32 contiguous tensor on this device (or a raw pointer: tris=(pointer, n)); a non-finite number gives the
+        empty set. max_dist2: optional [n] float32 tensor of squared bounds (+inf: none; 0: what touches; NaN or
+        negative: nothing). kind: an optional [n] int32 output that receives the winning candidate (0..2 a query
+        corner, 3..5 a mesh corner, 6..14 an edge pair, 15 a crossing, -1 the empty set). kernel="strict" tests every
+        triangle (the checker), "fast" / "auto" walks the full wide view with the same bits. tri / d2 / on_query /
+        on_mesh: optional outputs (allocated when not given). A zero-area query is answered by the fifteen candidates
+        alone. Asynchronous on the renderer's stream: sync() or clearance_info() before the results are read on
+        another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        pt, n = self._tris(tris)
+        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
+            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
+        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
+            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
+        for x, what in ((on_query, "on_query"), (on_mesh, "on_mesh")):
+            if isinstance(x, torch.Tensor) and (x.dim() != 2 or x.shape[1] != 3):
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, 3]")
+        pm = _ptr(max_dist2, "max_dist2", n, f32, self.device)
+        for x, what, m, dt in ((tri, "tri", n, i32), (d2, "d2", n, f32), (on_query, "on_query", 3 * n, f32),
+                               (on_mesh, "on_mesh", 3 * n, f32), (kind, "kind", n, i32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        if d2 is None:
+            d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        if on_query is None:
+            on_query = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if on_mesh is None:
+            on_mesh = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        res = _lib.ClearanceResults(_ptr(tri, "tri", n, i32, self.device), _ptr(d2, "d2", n, f32, self.device),
+                                    _ptr(on_query, "on_query", 3 * n, f32, self.device),
+                                    _ptr(on_mesh, "on_mesh", 3 * n, f32, self.device),
+                                    _ptr(kind, "kind", n, i32, self.device))
+        q = _lib.ClearTris(pt, pm, n, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_clearance_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_clearance_triangles")
+        return tri, d2, on_query, on_mesh
+
+    def clearance_info(self):
+        """rt_get_clearance_info: the last clearance query's counters (triangles, found, walked, exhaustive, empty,
+        nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed its
+        stack"""
+        i = _lib.ClearanceInfo()
+        self._chk(_L.rt_get_clearance_info(self._ctx, ctypes.byref(i)), "rt_get_clearance_info")
+        return {f: getattr(i, f) for f, _ in _lib.ClearanceInfo._fields_}
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

@@ -17,7 +17,9 @@ closest-hit query (hits_mode below), --mode nearest rt_nearest_p
 rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode below), --mode sweep
 rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below), --mode cuts
 rt_cut_triangles beside rt_overlap_boxes on the query triangles' corner boxes (cuts_mode below), --mode
-contacts rt_sweep_contacts beside rt_sweep_spheres on the same sweeps (contacts_mode below).
+contacts rt_sweep_contacts beside rt_sweep_spheres on the same sweeps (contacts_mode below), --mode
+clearance rt_clearance_triangles beside rt_cut_triangles' count on the same triangles and rt_nearest_points on their
+centroids (clearance_mode below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
@@ -26,7 +28,8 @@ usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --h
        python tools/query_bench.py --mode overlap [--runs 7] [--out profiles/overlap_bench_<md5>.jsonl]
        python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]
        python tools/query_bench.py --mode cuts [--runs 5] [--out profiles/cuts_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode contacts [--runs 5] [--out profiles/contacts_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode contacts [--runs 5] [--out profiles/contacts_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode clearance [--runs 5] [--out profiles/clearance_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -44,7 +47,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts",
-                                       "contacts"],
+                                       "contacts", "clearance"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
@@ -53,7 +56,9 @@ def main():
                          "overlap: rt_overlap_boxes beside rt_nearest_tris' radius count (overlap_mode); "
                          "sweep: rt_sweep_spheres beside the closest-hit query (sweep_mode); "
                          "cuts: rt_cut_triangles beside rt_overlap_boxes on the corner boxes (cuts_mode); "
-                         "contacts: rt_sweep_contacts beside rt_sweep_spheres (contacts_mode)")
+                         "contacts: rt_sweep_contacts beside rt_sweep_spheres (contacts_mode); "
+                         "clearance: rt_clearance_triangles beside rt_cut_triangles' count and rt_nearest_points "
+                         "(clearance_mode)")
     ap.add_argument("--out", default=None,
                     help="nearest, neighbours, overlap, sweep, cuts, contacts: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
@@ -79,6 +84,8 @@ def main():
         return cuts_mode(a, md5)
     if a.mode == "contacts":
         return contacts_mode(a, md5)
+    if a.mode == "clearance":
+        return clearance_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -770,6 +777,107 @@ def cuts_mode(a, md5):
             if total > CSR_CAP:
                 print(json.dumps({"scene": name, "set": label, "arm": "cut_csr", "skipped": "set_entries above the cap",
                                   "set_entries": total, "cap": CSR_CAP}), flush=True)
+        r.close()
+    if out:
+        out.close()
+
+
+def clearance_mode(a, md5):
+    """--mode clearance: per scene, rt_clearance_triangles on W x H query triangles (1920 x 1080 by
+    default): cuts_mode's triangles centred on the hit points of the camera's primary rays, with sizes of 0.1 %, 1 % and
+    5 % of the scene's extent, on the surface and lifted off it (the centre moved back along its ray by three times the
+    size), and a prt.tris.sheet beside the mesh (parallel to the low z face of the scene's box, a twentieth of the
+    extent outside it). Per set: the fast kernel, beside rt_cut_triangles' pure count on the same triangles (the walk
+    that answers "does it cross") and rt_nearest_points on their centroids (the walk that answers a point), and the
+    exhaustive kernel on 4,096 of the queries. One untimed round first; then --runs rounds with the arms interleaved;
+    kernel_ms from the HIP events around each launch. One JSON line per arm: median / min / max ms, the ratios of the
+    medians to the cut count's and to the nearest query's, the per-query ratio to the exhaustive kernel, nodes_visited,
+    pairs_tested and pairs_gated per query, the share of answers that are crossings, the counters, and whether the
+    fast kernel equals the exhaustive one on the 4,096 queries (every output's bits)."""
+    import numpy as np
+    import torch
+    from prt import device, host, tris
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        o, d, g, _ = point_sets(r, s, W, H)
+        hit, t = r.trace_rays(o, d, kernel="fast")
+        r.sync()
+        t = torch.where(hit >= 0, t, torch.ones_like(t))
+        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+        slo, shi = v.min(0), v.max(0)
+        ext = float((shi - slo).max())
+        off = torch.randn(n, 3, 3, generator=g)
+        off = (off - off.mean(dim=1, keepdim=True)).cuda()
+        sets = []
+        for pct in (0.1, 1.0, 5.0):
+            size = ext * pct / 100
+            for lift, what in ((0.0, "on"), (3.0 * size, "lifted")):
+                ctr = (o + d * (t - lift / d.norm(dim=1))[:, None]).contiguous()
+                sets.append((f"hit_points_{pct}pct_{what}", (ctr[:, None, :] + off * size).contiguous(), size))
+        dims = (1440, 720) if n == 2073600 else (W, max(H // 2, 1))
+        su = np.array([shi[0] - slo[0], 0.0, 0.0], np.float32)
+        sv = np.array([0.0, shi[1] - slo[1], 0.0], np.float32)
+        sheet = tris.sheet(np.array([slo[0], slo[1], slo[2] - 0.05 * ext], np.float32), su, sv, dims)
+        sets.append((f"sheet_beside_{dims[0]}x{dims[1]}", sheet, float(max(su[0] / dims[0], sv[1] / dims[1]))))
+        for label, q, size in sets:
+            m = len(q)
+            pick = torch.randperm(m, generator=g)[:NS].cuda()
+            qs = q[pick].contiguous()
+            cen = q.mean(dim=1).contiguous()
+            kind = torch.empty(m, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+
+            def clearance(p=q, kernel="fast", kd=None):
+                res = r.clearance(p, kernel=kernel, kind=kd)
+                return r.clearance_info(), res, len(p)
+
+            def cut_count():
+                res = r.cuts(q, k=0, count_all=True)
+                return r.cuts_info(), res, m
+
+            def nearest():
+                res = r.nearest(cen)
+                return r.nearest_info(), res, m
+
+            arms = [("clearance", lambda: clearance(kd=kind)), ("cut_count", cut_count), ("nearest_centroids", nearest),
+                    ("clearance_exhaustive_4096", lambda: clearance(qs, "strict"))]
+            ka, kb = (torch.empty(NS, dtype=torch.int32, device="cuda") for _ in range(2))
+            x, y = clearance(qs, "fast", ka)[1], clearance(qs, "strict", kb)[1]
+            same = all(bool((p.view(torch.int32) == w.view(torch.int32)).all()) for p, w in zip((*x, ka), (*y, kb)))
+            for _, fn in arms:  # the untimed round
+                fn()
+            crossing = float((kind == 15).float().mean())
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _, cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                tested = info["tris_tested"] if k == "nearest_centroids" else info["pairs_tested"]
+                line = {"scene": name, "set": label, "arm": k, "queries": cnt[k], "size": round(size, 6),
+                        "crossing_share": round(crossing, 4), "mqueries_s": round(cnt[k] / med[k] / 1e3, 2),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_cut_count": round((med[k] / cnt[k]) / (med["cut_count"] / m), 3),
+                        "ratio_to_nearest": round((med[k] / cnt[k]) / (med["nearest_centroids"] / m), 3),
+                        "per_query_ratio_to_exhaustive": round((med[k] / cnt[k]) /
+                                                               (med["clearance_exhaustive_4096"] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same if k == "clearance" else None,
+                        "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
+                        "tests_per_query": round(tested / cnt[k], 2),
+                        "gated_per_query": round(info.get("pairs_gated", 0) / cnt[k], 2),
+                        "info": {x: w for x, w in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
         r.close()
     if out:
         out.close()
