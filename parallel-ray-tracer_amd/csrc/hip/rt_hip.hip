@@ -31,6 +31,7 @@
 #include "rt_build.hpp"
 #include "rt_comm_logic.hpp"
 #include "rt_launch_logic.hpp"
+#include "rt_query_logic.hpp"
 #include "rt_treelet.hpp"
 #include "rt_feedback.hpp"
 #include "rt_query.hpp"
@@ -197,8 +198,6 @@ struct rt_ctx {
     };
     std::vector<BatchRule> brules;
     long long scene_gen = 0;  // bumped by every upload
-    // ray queries (rt_trace_rays, rt_query.hpp): their own counter block ([rtd::Q_NCOUNT] counters, then the chunk
-    // counter) and event pair -- nothing a render call owns is touched
     // vertex updates (rt_update_vertices, rt_refit.hpp): what the upload built and how (a view's rebuild repeats it),
     // the per-topology refit data of the five views, the plan pass's words, the face lists' sort buffers
     int built_accel = 0, ploc_radius = 0;
@@ -231,63 +230,20 @@ struct rt_ctx {
     float4* h_lights = nullptr;  // pinned staging of rt_update_lights, 2 x n_lights (freed with the scene)
     hipEvent_t lights_ev = nullptr;
     float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
-    unsigned long long* d_query = nullptr;
-    hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
-    bool queried = false, q_launched = false;
-    std::unordered_map<const void*, int> q_resident;  // resident workgroups of each k_query instantiation (resident())
-    // radiance queries (rt_shade_rays, rt_shade.hpp): the same again, their own ([rtd::S_NCOUNT] counters, then the
-    // chunk counter) -- a shade query touches neither a render's state nor rt_get_query_info's answer
-    unsigned long long* d_shq = nullptr;
-    hipEvent_t s_ev0 = nullptr, s_ev1 = nullptr;
-    bool shaded = false, s_launched = false;
-    std::unordered_map<const void*, int> s_resident;  // resident workgroups of each k_shade instantiation (0: none fits)
-    // multi-hit queries (rt_trace_hits, rt_hits.hpp): their own again ([rtd::H_NCOUNT] counters, then the chunk counter)
-    unsigned long long* d_hitq = nullptr;
-    hipEvent_t h_ev0 = nullptr, h_ev1 = nullptr;
-    bool hits_traced = false, h_launched = false;
-    std::unordered_map<const void*, int> h_resident;  // resident workgroups of each k_hits instantiation
-    // nearest-surface queries (rt_nearest_points, rt_nearest.hpp): their own again ([rtd::N_NCOUNT] counters, then the
-    // chunk counter)
-    unsigned long long* d_nearq = nullptr;
-    hipEvent_t n_ev0 = nullptr, n_ev1 = nullptr;
-    bool nearest_run = false, n_launched = false;
-    std::unordered_map<const void*, int> n_resident;  // resident workgroups of each k_nearest instantiation
-    // neighbour queries (rt_nearest_tris, rt_neighbours.hpp): their own again ([rtd::B_NCOUNT] counters, then the chunk
-    // counter); d_ref_inv: original triangle index -> position in the reference tree's records, made by the first
-    // query of a scene that asks for points (freed with the scene)
-    unsigned long long* d_nbq = nullptr;
-    hipEvent_t b_ev0 = nullptr, b_ev1 = nullptr;
-    bool neighbours_run = false, b_launched = false;
-    std::unordered_map<const void*, int> b_resident;  // resident workgroups of each k_neighbours instantiation
+    // the queries (rt_trace_rays ... rt_clearance_triangles): one slot per family (rtq::Fam), so that a query touches
+    // neither a render's state nor another family's info. counters: the family's [NCOUNT] counters, then its chunk
+    // counter (made by the family's first query); ev0, ev1: around its last launch; run: a query was accepted (its info
+    // can be read); launched: that query had n > 0, so the events were recorded
+    struct QuerySlot {
+        unsigned long long* counters = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        bool run = false, launched = false;
+    } slots[rtq::NFAM];
+    // resident workgroups of each query kernel, by its address (query_resident; 0: a k_shade build that does not fit)
+    std::unordered_map<const void*, int> residents;
+    // original triangle index -> position in the reference tree's records (ensure_ref_inv: made by the first neighbour
+    // or contact query of a scene that asks for points, freed with the scene)
     int* d_ref_inv = nullptr;
-    // overlap queries (rt_overlap_boxes, rt_overlap.hpp): their own again ([rtd::O_NCOUNT] counters, then the chunk
-    // counter)
-    unsigned long long* d_ovq = nullptr;
-    hipEvent_t o_ev0 = nullptr, o_ev1 = nullptr;
-    bool overlaps_run = false, o_launched = false;
-    std::unordered_map<const void*, int> o_resident;  // resident workgroups of each k_overlap instantiation
-    // sweep queries (rt_sweep_spheres, rt_sweep.hpp): their own again ([rtd::SW_NCOUNT] counters, then the chunk counter)
-    unsigned long long* d_swq = nullptr;
-    hipEvent_t w_ev0 = nullptr, w_ev1 = nullptr;
-    bool sweeps_run = false, w_launched = false;
-    std::unordered_map<const void*, int> w_resident;  // resident workgroups of each k_sweep instantiation
-    // contact queries (rt_sweep_contacts, rt_contacts.hpp): their own again ([rtd::CT_NCOUNT] counters, then the chunk
-    // counter); they share d_ref_inv with the neighbour queries
-    unsigned long long* d_ctq = nullptr;
-    hipEvent_t c_ev0 = nullptr, c_ev1 = nullptr;
-    bool contacts_run = false, c_launched = false;
-    std::unordered_map<const void*, int> c_resident;  // resident workgroups of each k_contacts instantiation
-    // cut queries (rt_cut_triangles, rt_cut.hpp): their own again ([rtd::X_NCOUNT] counters, then the chunk counter)
-    unsigned long long* d_cutq = nullptr;
-    hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;
-    bool cuts_run = false, x_launched = false;
-    std::unordered_map<const void*, int> x_resident;  // resident workgroups of each k_cut instantiation
-    // clearance queries (rt_clearance_triangles, rt_clearance.hpp): their own again ([rtd::CL_NCOUNT] counters, then the
-    // chunk counter)
-    unsigned long long* d_clq = nullptr;
-    hipEvent_t l_ev0 = nullptr, l_ev1 = nullptr;
-    bool clearance_run = false, l_launched = false;
-    std::unordered_map<const void*, int> l_resident;  // resident workgroups of each k_clearance instantiation
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
     // cold kernel), the trials and the choice
@@ -2201,6 +2157,113 @@ extern "C" int rt_get_launch_info(rt_ctx* ctx, rt_launch_info* info) {
     return RT_OK;
 }
 
+// ---------------------------------------------------------------- the queries' shared steps
+// An entry point reads: the checks (rtq::check_enter, the family's own, rtq::check_args), query_begin, fill A, pick the
+// kernel, query_launch. Its info call: query_read, the family's fields, query_finish.
+namespace {
+// The family's slot made ready for a new query, after every check (a refused call leaves the family's info as it was)
+// and before the n = 0 return (an empty query reports zero counters and no kernel time); A: the kernel's arguments,
+// cleared, with the slot's counters in them.
+template <class Args>
+int query_begin(rt_ctx* ctx, rtq::Fam f, int ncount, Args& A) {
+    rt_ctx::QuerySlot& q = ctx->slots[f];
+    HIPC(hipSetDevice(ctx->device));
+    const size_t cbytes = sizeof(unsigned long long) * (ncount + 1);
+    if (!q.counters) HIPC(hipMalloc((void**)&q.counters, cbytes));
+    if (!q.ev0) HIPC(hipEventCreate(&q.ev0));
+    if (!q.ev1) HIPC(hipEventCreate(&q.ev1));
+    HIPC(hipMemsetAsync(q.counters, 0, cbytes, ctx->stream));
+    q.run = true;
+    q.launched = false;
+    std::memset(&A, 0, sizeof A);
+    A.counters = q.counters;
+    A.work = reinterpret_cast<unsigned int*>(q.counters + ncount);
+    return RT_OK;
+}
+
+// resident workgroups of a query kernel with `dyn` bytes of dynamic LDS (the occupancy query once per kernel, not per
+// query); must_fit: 0 when a workgroup of it does not fit a CU, where the others count one per CU (resident())
+template <class K>
+int query_resident(rt_ctx* ctx, K k, size_t dyn = 0, bool must_fit = false) {
+    auto res = ctx->residents.find((const void*)k);
+    if (res != ctx->residents.end()) return res->second;
+    bool fits = true;
+    if (must_fit) {
+        int per_cu = 0;
+        fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, rtd::BLOCK, dyn) == hipSuccess && per_cu >= 1;
+        (void)hipGetLastError();
+    }
+    const int n = fits ? resident(k, ctx->device, 8, dyn) : 0;
+    ctx->residents.emplace((const void*)k, n);
+    return n;
+}
+
+// the kernel over A.n queries, between the slot's events
+template <class Args>
+int query_launch(rt_ctx* ctx, rtq::Fam f, void (*k)(Args), const Args& A, size_t dyn = 0) {
+    rt_ctx::QuerySlot& q = ctx->slots[f];
+    const int blocks = rtq::grid_blocks(A.n, rtd::QUERY_CHUNK, query_resident(ctx, k, dyn));
+    HIPC(hipEventRecord(q.ev0, ctx->stream));
+    k<<<blocks, rtd::BLOCK, dyn, ctx->stream>>>(A);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(q.ev1, ctx->stream));
+    q.launched = true;
+    return RT_OK;
+}
+
+// The counters of the family's last query into c (after a wait for the stream), and a cleared info; none_run: the
+// family's message when it has run none.
+template <class Info, size_t N>
+int query_read(rt_ctx* ctx, rtq::Fam f, const char* none_run, unsigned long long (&c)[N], Info* info) {
+    if (!ctx || !info) return RT_E_ARG;
+    if (!ctx->slots[f].run) {
+        ctx->err = none_run;
+        return RT_E_STATE;
+    }
+    HIPC(hipSetDevice(ctx->device));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    HIPC(hipMemcpy(c, ctx->slots[f].counters, sizeof c, hipMemcpyDeviceToHost));
+    std::memset(info, 0, sizeof *info);
+    return RT_OK;
+}
+
+// The kernel's time when one was launched, and RT_E_KERNEL when its walks overflowed a stack; too_deep: what was
+// (the three ray families walk every view, the other seven the wide view only).
+constexpr const char* DEEP_BVH = "BVH deeper than the walks' stacks";
+constexpr const char* DEEP_WIDE = "wide view deeper than the walk's stack";
+int query_finish(rt_ctx* ctx, rtq::Fam f, const char* who, unsigned long long overflows, const char* too_deep,
+                 float* kernel_ms) {
+    const rt_ctx::QuerySlot& q = ctx->slots[f];
+    if (q.launched) HIPC(hipEventElapsedTime(kernel_ms, q.ev0, q.ev1));
+    if (overflows) {
+        ctx->err = std::string(who) + ": the query's traversal stack overflowed " + std::to_string(overflows) +
+                   " times (" + too_deep + "): its results are not valid";
+        return RT_E_KERNEL;
+    }
+    return RT_OK;
+}
+
+// fn<CAP, STRICT> of a list family: the build with the smallest capacity that holds cap entries (rtq::list_capacity)
+#define FOR_LIST_CAP(cap, strict, fn)                                                          \
+    (rtq::list_capacity(cap) == 0   ? ((strict) ? fn<0, true> : fn<0, false>)                  \
+     : rtq::list_capacity(cap) == 4 ? ((strict) ? fn<4, true> : fn<4, false>)                  \
+     : rtq::list_capacity(cap) == 8 ? ((strict) ? fn<8, true> : fn<8, false>)                  \
+                                    : ((strict) ? fn<16, true> : fn<16, false>))
+
+// d_ref_inv of the scene (rt_neighbours.hpp ref_inv), made on first use
+int ensure_ref_inv(rt_ctx* ctx) {
+    if (ctx->d_ref_inv) return RT_OK;
+    const int nt = ctx->n_tris;
+    HIPC(hipMalloc((void**)&ctx->d_ref_inv, sizeof(int) * (size_t)std::max(nt, 1)));
+    HIPC(hipMemsetAsync(ctx->d_ref_inv, 0, sizeof(int) * (size_t)std::max(nt, 1), ctx->stream));
+    if (nt > 0) {
+        rtd::k_invert_orig<<<(nt + 255) / 256, 256, 0, ctx->stream>>>(ctx->ref.orig, nt, ctx->d_ref_inv);
+        HIPC(hipGetLastError());
+    }
+    return RT_OK;
+}
+}  // namespace
+
 // ---------------------------------------------------------------- ray queries (rt_query.hpp)
 namespace {
 using QFn = void (*)(rtd::QArgs);
@@ -2218,14 +2281,9 @@ QFn query_kernel(int kind, bool strict, bool tq, bool pool) {
 
 extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results* out) {
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_trace_rays: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_trace_rays: null rays / results");
+    if (int rc = rtq::check_enter(rtq::RAYS, ctx->has_scene, r && out, ctx->err)) return rc;
     if (r->kind != RT_QUERY_CLOSEST && r->kind != RT_QUERY_OCCLUDED) return arg_err(ctx, "rt_trace_rays: bad kind");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_trace_rays: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_trace_rays: negative ray count");
+    if (int rc = rtq::check_args(rtq::RAYS, r->kernel, r->n, ctx->err)) return rc;
     if (r->regroup < 0 || r->regroup > 64) return arg_err(ctx, "rt_trace_rays: regroup must be 0..64");
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_trace_rays: null origin / dir");
@@ -2233,16 +2291,9 @@ extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results
         return arg_err(ctx, "rt_trace_rays: RT_QUERY_OCCLUDED needs max_dist2 and an occluded output");
     if (r->n > 0 && r->kind == RT_QUERY_CLOSEST && !out->hit && !out->t)
         return arg_err(ctx, "rt_trace_rays: RT_QUERY_CLOSEST needs a hit or a t output");
-    HIPC(hipSetDevice(ctx->device));
-    if (!ctx->d_query) HIPC(hipMalloc((void**)&ctx->d_query, sizeof(unsigned long long) * (rtd::Q_NCOUNT + 1)));
-    if (!ctx->q_ev0) HIPC(hipEventCreate(&ctx->q_ev0));
-    if (!ctx->q_ev1) HIPC(hipEventCreate(&ctx->q_ev1));
-    HIPC(hipMemsetAsync(ctx->d_query, 0, sizeof(unsigned long long) * (rtd::Q_NCOUNT + 1), ctx->stream));
-    ctx->queried = true;
-    ctx->q_launched = false;
-    if (r->n == 0) return RT_OK;
     rtd::QArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::RAYS, rtd::Q_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the primary view is chosen per ray)
     A.origin = r->origin;
     A.dir = r->dir;
@@ -2250,8 +2301,6 @@ extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results
     A.hit = out->hit;
     A.t = out->t;
     A.occluded = out->occluded;
-    A.counters = ctx->d_query;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_query + rtd::Q_NCOUNT);
     A.n = r->n;
     A.o_max = 4.0f * ctx->scene_mx;
     const bool strict = r->kernel == RT_KERNEL_STRICT;
@@ -2259,30 +2308,12 @@ extern "C" int rt_trace_rays(rt_ctx* ctx, const rt_rays* r, const rt_ray_results
     // threshold in idle lanes (0: 16), 64 = the lockstep form instead. The closest-hit query has the lockstep form only.
     const bool pool = r->kind == RT_QUERY_OCCLUDED && !strict && ctx->wide.n > 0 && r->regroup != 64;
     A.regroup = r->regroup > 0 ? r->regroup : 16;
-    const QFn k = query_kernel(r->kind, strict, ctx->tq_ok, pool);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->q_resident.find((const void*)k);  // (the occupancy query once per kernel, not per query)
-    if (res == ctx->q_resident.end()) res = ctx->q_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->q_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->q_ev1, ctx->stream));
-    ctx->q_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::RAYS, query_kernel(r->kind, strict, ctx->tq_ok, pool), A);
 }
 
 extern "C" int rt_get_query_info(rt_ctx* ctx, rt_query_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->queried) {
-        ctx->err = "rt_get_query_info: no query traced";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::Q_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_query, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::RAYS, "rt_get_query_info: no query traced", c, info)) return rc;
     info->rays = (long long)c[rtd::Q_RAYS];
     info->hits = (long long)c[rtd::Q_HITS];
     info->unit_rays = (long long)c[rtd::Q_UNIT];
@@ -2291,13 +2322,7 @@ extern "C" int rt_get_query_info(rt_ctx* ctx, rt_query_info* info) {
     info->strict_rays = (long long)c[rtd::Q_STRICT];
     info->tie_rewalks = (long long)c[rtd::Q_TIE];
     info->stack_overflows = (long long)c[rtd::Q_ERR];
-    if (ctx->q_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->q_ev0, ctx->q_ev1));
-    if (c[rtd::Q_ERR]) {
-        ctx->err = "rt_get_query_info: the query's traversal stack overflowed " + std::to_string(c[rtd::Q_ERR]) +
-                   " times (BVH deeper than the walks' stacks): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::RAYS, "rt_get_query_info", c[rtd::Q_ERR], DEEP_BVH, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- vertex updates (rt_refit.hpp)
@@ -3052,18 +3077,6 @@ SFn shade_kernel(int bounces, bool strict, bool tq, bool pool) {
 template <int MAXB>
 size_t shade_lds_of(bool tq) { return rtd::shade_pool_lds<MAXB>(tq); }
 size_t shade_lds(int bounces, bool tq) { return FOR_MAXB(bounces, shade_lds_of, tq); }
-// resident workgroups of a k_shade instantiation with `dyn` bytes of dynamic LDS (asked once per kernel); 0: a
-// workgroup of it does not fit a CU
-int shade_resident(rt_ctx* ctx, SFn k, size_t dyn) {
-    auto res = ctx->s_resident.find((const void*)k);
-    if (res != ctx->s_resident.end()) return res->second;
-    int per_cu = 0;
-    const bool fits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, rtd::BLOCK, dyn) == hipSuccess && per_cu >= 1;
-    (void)hipGetLastError();
-    const int n = fits ? resident(k, ctx->device, 8, dyn) : 0;
-    ctx->s_resident.emplace((const void*)k, n);
-    return n;
-}
 // The library's choice for regroup = 0: the pool form at 16 idle lanes (measured, DESIGN.md §3l: 28 % less time than
 // the lockstep form on dragon's row-major camera rays, 3 % more on car_boxed's).
 constexpr int SHADE_REGROUP_DEFAULT = 16;
@@ -3071,13 +3084,8 @@ constexpr int SHADE_REGROUP_DEFAULT = 16;
 
 extern "C" int rt_shade_rays(rt_ctx* ctx, const rt_shade* r, const rt_shade_results* out) {
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_shade_rays: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_shade_rays: null rays / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_shade_rays: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_shade_rays: negative ray count");
+    if (int rc = rtq::check_enter(rtq::SHADE, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::SHADE, r->kernel, r->n, ctx->err)) return rc;
     if (r->bounces < 1 || r->bounces > 8) return arg_err(ctx, "rt_shade_rays: bounces must be 1..8");
     if (r->regroup < 0 || r->regroup > 64) return arg_err(ctx, "rt_shade_rays: regroup must be 0..64");
     if (r->unclamped != 0 && r->unclamped != 1) return arg_err(ctx, "rt_shade_rays: unclamped must be 0 or 1");
@@ -3086,17 +3094,9 @@ extern "C" int rt_shade_rays(rt_ctx* ctx, const rt_shade* r, const rt_shade_resu
     if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_shade_rays: null origin / dir");
     if (r->n > 0 && !out->rgb && !out->bgra && !out->hit && !out->t && !out->bounce_hit)
         return arg_err(ctx, "rt_shade_rays: no output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::S_NCOUNT + 1);
-    if (!ctx->d_shq) HIPC(hipMalloc((void**)&ctx->d_shq, cbytes));
-    if (!ctx->s_ev0) HIPC(hipEventCreate(&ctx->s_ev0));
-    if (!ctx->s_ev1) HIPC(hipEventCreate(&ctx->s_ev1));
-    HIPC(hipMemsetAsync(ctx->d_shq, 0, cbytes, ctx->stream));
-    ctx->shaded = true;
-    ctx->s_launched = false;
-    if (r->n == 0) return RT_OK;
     rtd::SArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::SHADE, rtd::S_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the primary view is chosen per ray)
     A.origin = r->origin;
     A.dir = r->dir;
@@ -3105,8 +3105,6 @@ extern "C" int rt_shade_rays(rt_ctx* ctx, const rt_shade* r, const rt_shade_resu
     A.hit = out->hit;
     A.t = out->t;
     A.bounce_hit = out->bounce_hit;
-    A.counters = ctx->d_shq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_shq + rtd::S_NCOUNT);
     A.n = r->n;
     A.bounces = r->bounces;
     A.o_max = 4.0f * ctx->scene_mx;
@@ -3117,42 +3115,26 @@ extern "C" int rt_shade_rays(rt_ctx* ctx, const rt_shade* r, const rt_shade_resu
     const int regroup = r->regroup > 0 ? r->regroup : SHADE_REGROUP_DEFAULT;
     bool pool = !strict && regroup != 64 && ctx->wide.n > 0 && ctx->n_lights <= 8 && ctx->pk_ok;
     A.regroup = regroup;
+    // (a k_shade build counts 0 resident workgroups when one does not fit a CU: query_resident's must_fit)
     SFn k = nullptr;
     size_t dyn = 0;
-    int res = 0;
     if (pool) {
         k = shade_kernel(r->bounces, false, ctx->tq_ok, true);
         dyn = shade_lds(r->bounces, ctx->tq_ok);
-        res = shade_resident(ctx, k, dyn);
-        if (res == 0) pool = false;  // its LDS does not fit: the lockstep form
+        if (query_resident(ctx, k, dyn, true) == 0) pool = false;  // its LDS does not fit: the lockstep form
     }
     if (!pool) {
         k = shade_kernel(r->bounces, strict, ctx->tq_ok, false);
         dyn = 0;
-        res = shade_resident(ctx, k, 0);
-        if (res == 0) return arg_err(ctx, "rt_shade_rays: the kernel does not fit this device");
+        if (query_resident(ctx, k, 0, true) == 0)
+            return arg_err(ctx, "rt_shade_rays: the kernel does not fit this device");
     }
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    const int blocks = std::max(1, std::min(res, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->s_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, dyn, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->s_ev1, ctx->stream));
-    ctx->s_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::SHADE, k, A, dyn);
 }
 
 extern "C" int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->shaded) {
-        ctx->err = "rt_get_shade_info: no rays shaded";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::S_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_shq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::SHADE, "rt_get_shade_info: no rays shaded", c, info)) return rc;
     info->rays = (long long)c[rtd::S_RAYS];
     info->hits = (long long)c[rtd::S_HITS];
     info->reflection = (long long)c[rtd::S_REFL];
@@ -3161,58 +3143,24 @@ extern "C" int rt_get_shade_info(rt_ctx* ctx, rt_shade_info* info) {
     info->strict_paths = (long long)c[rtd::S_STRICT];
     info->tie_rewalks = (long long)c[rtd::S_TIE];
     info->stack_overflows = (long long)c[rtd::S_ERR];
-    if (ctx->s_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->s_ev0, ctx->s_ev1));
-    if (c[rtd::S_ERR]) {
-        ctx->err = "rt_get_shade_info: the query's traversal stack overflowed " + std::to_string(c[rtd::S_ERR]) +
-                   " times (BVH deeper than the walks' stacks): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::SHADE, "rt_get_shade_info", c[rtd::S_ERR], DEEP_BVH, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- multi-hit queries (rt_hits.hpp)
-namespace {
-using HFn = void (*)(rtd::HArgs);
-// the smallest list capacity that holds max_hits (0: the counting build)
-HFn hits_kernel(int max_hits, bool strict) {
-    using rtd::k_hits;
-    if (max_hits == 0) return strict ? k_hits<0, true> : k_hits<0, false>;
-    if (max_hits <= 4) return strict ? k_hits<4, true> : k_hits<4, false>;
-    if (max_hits <= 8) return strict ? k_hits<8, true> : k_hits<8, false>;
-    return strict ? k_hits<16, true> : k_hits<16, false>;
-}
-}  // namespace
-
 extern "C" int rt_trace_hits(rt_ctx* ctx, const rt_hits* r, const rt_hit_results* out) {
-    static_assert(RT_HITS_MAX == rtd::HITS_MAX, "rt_hip.h and rt_hits.hpp must agree");
+    static_assert(RT_HITS_MAX == rtd::HITS_MAX && RT_HITS_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_hits.hpp and rt_query_logic.hpp must agree");
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_trace_hits: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_trace_hits: null rays / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_trace_hits: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_trace_hits: negative ray count");
-    if (r->max_hits < 0 || r->max_hits > RT_HITS_MAX) return arg_err(ctx, "rt_trace_hits: max_hits must be 0..16");
-    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_trace_hits: count_all must be 0 or 1");
-    if (r->max_hits == 0 && !r->count_all) return arg_err(ctx, "rt_trace_hits: max_hits = 0 needs count_all");
+    if (int rc = rtq::check_enter(rtq::HITS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::HITS, r->kernel, r->n, r->max_hits, r->count_all, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && (!r->origin || !r->dir)) return arg_err(ctx, "rt_trace_hits: null origin / dir");
     if (r->n > 0 && r->max_hits > 0 && !out->tri && !out->t)
         return arg_err(ctx, "rt_trace_hits: max_hits > 0 needs a tri or a t output");
-    if (r->n > 0 && r->max_hits == 0 && !out->count)
-        return arg_err(ctx, "rt_trace_hits: a counting query needs a count output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::H_NCOUNT + 1);
-    if (!ctx->d_hitq) HIPC(hipMalloc((void**)&ctx->d_hitq, cbytes));
-    if (!ctx->h_ev0) HIPC(hipEventCreate(&ctx->h_ev0));
-    if (!ctx->h_ev1) HIPC(hipEventCreate(&ctx->h_ev1));
-    HIPC(hipMemsetAsync(ctx->d_hitq, 0, cbytes, ctx->stream));
-    ctx->hits_traced = true;
-    ctx->h_launched = false;
-    if (r->n == 0) return RT_OK;
+    if (int rc = rtq::check_count_out(rtq::HITS, r->n, r->max_hits, out->count != nullptr, ctx->err)) return rc;
     rtd::HArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::HITS, rtd::H_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the view is chosen per ray)
     A.origin = r->origin;
     A.dir = r->dir;
@@ -3220,36 +3168,16 @@ extern "C" int rt_trace_hits(rt_ctx* ctx, const rt_hits* r, const rt_hit_results
     A.tri = out->tri;
     A.t = out->t;
     A.count = out->count;
-    A.counters = ctx->d_hitq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_hitq + rtd::H_NCOUNT);
     A.n = r->n;
     A.o_max = 4.0f * ctx->scene_mx;
     A.max_hits = r->max_hits;
     A.count_all = r->count_all;
-    const HFn k = hits_kernel(r->max_hits, r->kernel == RT_KERNEL_STRICT);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->h_resident.find((const void*)k);
-    if (res == ctx->h_resident.end()) res = ctx->h_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->h_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->h_ev1, ctx->stream));
-    ctx->h_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::HITS, FOR_LIST_CAP(r->max_hits, r->kernel == RT_KERNEL_STRICT, rtd::k_hits), A);
 }
 
 extern "C" int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->hits_traced) {
-        ctx->err = "rt_get_hits_info: no hits query traced";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::H_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_hitq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::HITS, "rt_get_hits_info: no hits query traced", c, info)) return rc;
     info->rays = (long long)c[rtd::H_RAYS];
     info->rays_hit = (long long)c[rtd::H_RAYS_HIT];
     info->hits_stored = (long long)c[rtd::H_STORED];
@@ -3259,73 +3187,35 @@ extern "C" int rt_get_hits_info(rt_ctx* ctx, rt_hits_info* info) {
     info->full_rays = (long long)c[rtd::H_FULL];
     info->exhaustive_rays = (long long)c[rtd::H_EXH];
     info->stack_overflows = (long long)c[rtd::H_ERR];
-    if (ctx->h_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->h_ev0, ctx->h_ev1));
-    if (c[rtd::H_ERR]) {
-        ctx->err = "rt_get_hits_info: the query's traversal stack overflowed " + std::to_string(c[rtd::H_ERR]) +
-                   " times (BVH deeper than the walks' stacks): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::HITS, "rt_get_hits_info", c[rtd::H_ERR], DEEP_BVH, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- nearest-surface queries (rt_nearest.hpp)
 extern "C" int rt_nearest_points(rt_ctx* ctx, const rt_points* r, const rt_nearest_results* out) {
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_nearest_points: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_nearest_points: null points / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_nearest_points: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_nearest_points: negative point count");
+    if (int rc = rtq::check_enter(rtq::NEAREST, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::NEAREST, r->kernel, r->n, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && !r->point) return arg_err(ctx, "rt_nearest_points: null point");
     if (r->n > 0 && !out->tri && !out->d2 && !out->point)
         return arg_err(ctx, "rt_nearest_points: needs a tri, a d2 or a point output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::N_NCOUNT + 1);
-    if (!ctx->d_nearq) HIPC(hipMalloc((void**)&ctx->d_nearq, cbytes));
-    if (!ctx->n_ev0) HIPC(hipEventCreate(&ctx->n_ev0));
-    if (!ctx->n_ev1) HIPC(hipEventCreate(&ctx->n_ev1));
-    HIPC(hipMemsetAsync(ctx->d_nearq, 0, cbytes, ctx->stream));
-    ctx->nearest_run = true;
-    ctx->n_launched = false;
-    if (r->n == 0) return RT_OK;
     rtd::NArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::NEAREST, rtd::N_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.point = r->point;
     A.max_dist2 = r->max_dist2;
     A.tri = out->tri;
     A.d2 = out->d2;
     A.out = out->point;
-    A.counters = ctx->d_nearq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_nearq + rtd::N_NCOUNT);
     A.n = r->n;
     void (*k)(rtd::NArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_nearest<true> : rtd::k_nearest<false>;
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->n_resident.find((const void*)k);
-    if (res == ctx->n_resident.end()) res = ctx->n_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->n_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->n_ev1, ctx->stream));
-    ctx->n_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::NEAREST, k, A);
 }
 
 extern "C" int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->nearest_run) {
-        ctx->err = "rt_get_nearest_info: no nearest query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::N_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_nearq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::NEAREST, "rt_get_nearest_info: no nearest query run", c, info)) return rc;
     info->points = (long long)c[rtd::N_POINTS];
     info->found = (long long)c[rtd::N_FOUND];
     info->walked_points = (long long)c[rtd::N_WALKED];
@@ -3334,68 +3224,27 @@ extern "C" int rt_get_nearest_info(rt_ctx* ctx, rt_nearest_info* info) {
     info->nodes_visited = (long long)c[rtd::N_NODES];
     info->tris_tested = (long long)c[rtd::N_TRIS];
     info->stack_overflows = (long long)c[rtd::N_ERR];
-    if (ctx->n_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->n_ev0, ctx->n_ev1));
-    if (c[rtd::N_ERR]) {
-        ctx->err = "rt_get_nearest_info: the query's traversal stack overflowed " + std::to_string(c[rtd::N_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::NEAREST, "rt_get_nearest_info", c[rtd::N_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- neighbour queries (rt_neighbours.hpp)
-namespace {
-using BFn = void (*)(rtd::BArgs);
-// the smallest list capacity that holds max_tris (0: the counting build)
-BFn neighbours_kernel(int max_tris, bool strict) {
-    using rtd::k_neighbours;
-    if (max_tris == 0) return strict ? k_neighbours<0, true> : k_neighbours<0, false>;
-    if (max_tris <= 4) return strict ? k_neighbours<4, true> : k_neighbours<4, false>;
-    if (max_tris <= 8) return strict ? k_neighbours<8, true> : k_neighbours<8, false>;
-    return strict ? k_neighbours<16, true> : k_neighbours<16, false>;
-}
-}  // namespace
-
 extern "C" int rt_nearest_tris(rt_ctx* ctx, const rt_neighbours* r, const rt_neighbour_results* out) {
-    static_assert(RT_NEIGHBOURS_MAX == rtd::NEIGHBOURS_MAX, "rt_hip.h and rt_neighbours.hpp must agree");
+    static_assert(RT_NEIGHBOURS_MAX == rtd::NEIGHBOURS_MAX && RT_NEIGHBOURS_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_neighbours.hpp and rt_query_logic.hpp must agree");
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_nearest_tris: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_nearest_tris: null points / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_nearest_tris: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_nearest_tris: negative point count");
-    if (r->max_tris < 0 || r->max_tris > RT_NEIGHBOURS_MAX) return arg_err(ctx, "rt_nearest_tris: max_tris must be 0..16");
-    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_nearest_tris: count_all must be 0 or 1");
-    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_nearest_tris: max_tris = 0 needs count_all");
+    if (int rc = rtq::check_enter(rtq::NEIGHBOURS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::NEIGHBOURS, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && !r->point) return arg_err(ctx, "rt_nearest_tris: null point");
     if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->d2 && !out->point)
         return arg_err(ctx, "rt_nearest_tris: max_tris > 0 needs a tri, a d2 or a point output");
-    if (r->n > 0 && r->max_tris == 0 && !out->count)
-        return arg_err(ctx, "rt_nearest_tris: a counting query needs a count output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::B_NCOUNT + 1);
-    if (!ctx->d_nbq) HIPC(hipMalloc((void**)&ctx->d_nbq, cbytes));
-    if (!ctx->b_ev0) HIPC(hipEventCreate(&ctx->b_ev0));
-    if (!ctx->b_ev1) HIPC(hipEventCreate(&ctx->b_ev1));
-    HIPC(hipMemsetAsync(ctx->d_nbq, 0, cbytes, ctx->stream));
-    ctx->neighbours_run = true;
-    ctx->b_launched = false;
+    if (int rc = rtq::check_count_out(rtq::NEIGHBOURS, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
+    rtd::BArgs A;
+    if (int rc = query_begin(ctx, rtq::NEIGHBOURS, rtd::B_NCOUNT, A)) return rc;
     if (r->n == 0) return RT_OK;
     const bool want_p = r->max_tris > 0 && out->point;
-    if (want_p && !ctx->d_ref_inv) {  // original index -> the reference tree's record (rt_neighbours.hpp ref_inv)
-        const int nt = ctx->n_tris;
-        HIPC(hipMalloc((void**)&ctx->d_ref_inv, sizeof(int) * (size_t)std::max(nt, 1)));
-        HIPC(hipMemsetAsync(ctx->d_ref_inv, 0, sizeof(int) * (size_t)std::max(nt, 1), ctx->stream));
-        if (nt > 0) {
-            rtd::k_invert_orig<<<(nt + 255) / 256, 256, 0, ctx->stream>>>(ctx->ref.orig, nt, ctx->d_ref_inv);
-            HIPC(hipGetLastError());
-        }
-    }
-    rtd::BArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (want_p)
+        if (int rc = ensure_ref_inv(ctx)) return rc;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.point = r->point;
     A.max_dist2 = r->max_dist2;
@@ -3404,35 +3253,17 @@ extern "C" int rt_nearest_tris(rt_ctx* ctx, const rt_neighbours* r, const rt_nei
     A.out = want_p ? out->point : nullptr;
     A.count = out->count;
     A.ref_inv = ctx->d_ref_inv;
-    A.counters = ctx->d_nbq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_nbq + rtd::B_NCOUNT);
     A.n = r->n;
     A.max_tris = r->max_tris;
     A.count_all = r->count_all;
-    const BFn k = neighbours_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->b_resident.find((const void*)k);
-    if (res == ctx->b_resident.end()) res = ctx->b_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->b_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->b_ev1, ctx->stream));
-    ctx->b_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::NEIGHBOURS, FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_neighbours),
+                        A);
 }
 
 extern "C" int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->neighbours_run) {
-        ctx->err = "rt_get_neighbours_info: no neighbours query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::B_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_nbq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::NEIGHBOURS, "rt_get_neighbours_info: no neighbours query run", c, info))
+        return rc;
     info->points = (long long)c[rtd::B_POINTS];
     info->found = (long long)c[rtd::B_FOUND];
     info->tris_stored = (long long)c[rtd::B_STORED];
@@ -3443,59 +3274,25 @@ extern "C" int rt_get_neighbours_info(rt_ctx* ctx, rt_neighbours_info* info) {
     info->nodes_visited = (long long)c[rtd::B_NODES];
     info->tris_tested = (long long)c[rtd::B_TRIS];
     info->stack_overflows = (long long)c[rtd::B_ERR];
-    if (ctx->b_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->b_ev0, ctx->b_ev1));
-    if (c[rtd::B_ERR]) {
-        ctx->err = "rt_get_neighbours_info: the query's traversal stack overflowed " + std::to_string(c[rtd::B_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::NEIGHBOURS, "rt_get_neighbours_info", c[rtd::B_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- overlap queries (rt_overlap.hpp)
-namespace {
-using OFn = void (*)(rtd::OArgs);
-// the smallest list capacity that holds max_tris (0: the counting build)
-OFn overlap_kernel(int max_tris, bool strict) {
-    using rtd::k_overlap;
-    if (max_tris == 0) return strict ? k_overlap<0, true> : k_overlap<0, false>;
-    if (max_tris <= 4) return strict ? k_overlap<4, true> : k_overlap<4, false>;
-    if (max_tris <= 8) return strict ? k_overlap<8, true> : k_overlap<8, false>;
-    return strict ? k_overlap<16, true> : k_overlap<16, false>;
-}
-}  // namespace
-
 extern "C" int rt_overlap_boxes(rt_ctx* ctx, const rt_boxes* r, const rt_overlap_results* out) {
-    static_assert(RT_OVERLAPS_MAX == rtd::OVERLAPS_MAX, "rt_hip.h and rt_overlap.hpp must agree");
+    static_assert(RT_OVERLAPS_MAX == rtd::OVERLAPS_MAX && RT_OVERLAPS_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_overlap.hpp and rt_query_logic.hpp must agree");
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_overlap_boxes: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_overlap_boxes: null boxes / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_overlap_boxes: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_overlap_boxes: negative box count");
-    if (r->max_tris < 0 || r->max_tris > RT_OVERLAPS_MAX) return arg_err(ctx, "rt_overlap_boxes: max_tris must be 0..16");
-    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_overlap_boxes: count_all must be 0 or 1");
-    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_overlap_boxes: max_tris = 0 needs count_all");
+    if (int rc = rtq::check_enter(rtq::OVERLAPS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::OVERLAPS, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
     if ((r->offsets != nullptr) != (out->list != nullptr))
         return arg_err(ctx, "rt_overlap_boxes: offsets and list are given together or not at all");
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && (!r->lo || !r->hi)) return arg_err(ctx, "rt_overlap_boxes: null lo / hi");
     if (r->n > 0 && r->max_tris > 0 && !out->tri) return arg_err(ctx, "rt_overlap_boxes: max_tris > 0 needs a tri output");
-    if (r->n > 0 && r->max_tris == 0 && !out->count)
-        return arg_err(ctx, "rt_overlap_boxes: a counting query needs a count output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::O_NCOUNT + 1);
-    if (!ctx->d_ovq) HIPC(hipMalloc((void**)&ctx->d_ovq, cbytes));
-    if (!ctx->o_ev0) HIPC(hipEventCreate(&ctx->o_ev0));
-    if (!ctx->o_ev1) HIPC(hipEventCreate(&ctx->o_ev1));
-    HIPC(hipMemsetAsync(ctx->d_ovq, 0, cbytes, ctx->stream));
-    ctx->overlaps_run = true;
-    ctx->o_launched = false;
-    if (r->n == 0) return RT_OK;
+    if (int rc = rtq::check_count_out(rtq::OVERLAPS, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
     rtd::OArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::OVERLAPS, rtd::O_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.lo = r->lo;
     A.hi = r->hi;
@@ -3503,35 +3300,16 @@ extern "C" int rt_overlap_boxes(rt_ctx* ctx, const rt_boxes* r, const rt_overlap
     A.tri = r->max_tris > 0 ? out->tri : nullptr;
     A.count = out->count;
     A.list = out->list;
-    A.counters = ctx->d_ovq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_ovq + rtd::O_NCOUNT);
     A.n = r->n;
     A.max_tris = r->max_tris;
     A.count_all = r->count_all;
-    const OFn k = overlap_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->o_resident.find((const void*)k);
-    if (res == ctx->o_resident.end()) res = ctx->o_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->o_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->o_ev1, ctx->stream));
-    ctx->o_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::OVERLAPS, FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_overlap),
+                        A);
 }
 
 extern "C" int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->overlaps_run) {
-        ctx->err = "rt_get_overlaps_info: no overlap query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::O_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_ovq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::OVERLAPS, "rt_get_overlaps_info: no overlap query run", c, info)) return rc;
     info->boxes = (long long)c[rtd::O_BOXES];
     info->found = (long long)c[rtd::O_FOUND];
     info->tris_stored = (long long)c[rtd::O_STORED];
@@ -3543,41 +3321,22 @@ extern "C" int rt_get_overlaps_info(rt_ctx* ctx, rt_overlaps_info* info) {
     info->nodes_visited = (long long)c[rtd::O_NODES];
     info->tris_tested = (long long)c[rtd::O_TRIS];
     info->stack_overflows = (long long)c[rtd::O_ERR];
-    if (ctx->o_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->o_ev0, ctx->o_ev1));
-    if (c[rtd::O_ERR]) {
-        ctx->err = "rt_get_overlaps_info: the query's traversal stack overflowed " + std::to_string(c[rtd::O_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::OVERLAPS, "rt_get_overlaps_info", c[rtd::O_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- sweep queries (rt_sweep.hpp)
 extern "C" int rt_sweep_spheres(rt_ctx* ctx, const rt_spheres* r, const rt_sweep_results* out) {
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_sweep_spheres: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_sweep_spheres: null spheres / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_sweep_spheres: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_sweep_spheres: negative sphere count");
+    if (int rc = rtq::check_enter(rtq::SWEEP, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::SWEEP, r->kernel, r->n, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && (!r->centre || !r->motion || !r->radius))
         return arg_err(ctx, "rt_sweep_spheres: null centre / motion / radius");
     if (r->n > 0 && !out->tri && !out->t && !out->point)
         return arg_err(ctx, "rt_sweep_spheres: needs a tri, a t or a point output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::SW_NCOUNT + 1);
-    if (!ctx->d_swq) HIPC(hipMalloc((void**)&ctx->d_swq, cbytes));
-    if (!ctx->w_ev0) HIPC(hipEventCreate(&ctx->w_ev0));
-    if (!ctx->w_ev1) HIPC(hipEventCreate(&ctx->w_ev1));
-    HIPC(hipMemsetAsync(ctx->d_swq, 0, cbytes, ctx->stream));
-    ctx->sweeps_run = true;
-    ctx->w_launched = false;
-    if (r->n == 0) return RT_OK;
     rtd::SWArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::SWEEP, rtd::SW_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.centre = r->centre;
     A.motion = r->motion;
@@ -3586,34 +3345,15 @@ extern "C" int rt_sweep_spheres(rt_ctx* ctx, const rt_spheres* r, const rt_sweep
     A.tri = out->tri;
     A.t = out->t;
     A.out = out->point;
-    A.counters = ctx->d_swq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_swq + rtd::SW_NCOUNT);
     A.n = r->n;
     A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::sweep_domain
     void (*k)(rtd::SWArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_sweep<true> : rtd::k_sweep<false>;
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->w_resident.find((const void*)k);
-    if (res == ctx->w_resident.end()) res = ctx->w_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->w_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->w_ev1, ctx->stream));
-    ctx->w_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::SWEEP, k, A);
 }
 
 extern "C" int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->sweeps_run) {
-        ctx->err = "rt_get_sweep_info: no sweep query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::SW_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_swq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::SWEEP, "rt_get_sweep_info: no sweep query run", c, info)) return rc;
     info->spheres = (long long)c[rtd::SW_SPHERES];
     info->found = (long long)c[rtd::SW_FOUND];
     info->empty_spheres = (long long)c[rtd::SW_EMPTY];
@@ -3622,69 +3362,28 @@ extern "C" int rt_get_sweep_info(rt_ctx* ctx, rt_sweep_info* info) {
     info->nodes_visited = (long long)c[rtd::SW_NODES];
     info->tris_tested = (long long)c[rtd::SW_TRIS];
     info->stack_overflows = (long long)c[rtd::SW_ERR];
-    if (ctx->w_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->w_ev0, ctx->w_ev1));
-    if (c[rtd::SW_ERR]) {
-        ctx->err = "rt_get_sweep_info: the query's traversal stack overflowed " + std::to_string(c[rtd::SW_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::SWEEP, "rt_get_sweep_info", c[rtd::SW_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- contact queries (rt_contacts.hpp)
-namespace {
-using CFn = void (*)(rtd::CArgs);
-// the smallest list capacity that holds max_tris (0: the counting build)
-CFn contacts_kernel(int max_tris, bool strict) {
-    using rtd::k_contacts;
-    if (max_tris == 0) return strict ? k_contacts<0, true> : k_contacts<0, false>;
-    if (max_tris <= 4) return strict ? k_contacts<4, true> : k_contacts<4, false>;
-    if (max_tris <= 8) return strict ? k_contacts<8, true> : k_contacts<8, false>;
-    return strict ? k_contacts<16, true> : k_contacts<16, false>;
-}
-}  // namespace
-
 extern "C" int rt_sweep_contacts(rt_ctx* ctx, const rt_sphere_contacts* r, const rt_contact_results* out) {
-    static_assert(RT_CONTACTS_MAX == rtd::CONTACTS_MAX, "rt_hip.h and rt_contacts.hpp must agree");
+    static_assert(RT_CONTACTS_MAX == rtd::CONTACTS_MAX && RT_CONTACTS_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_contacts.hpp and rt_query_logic.hpp must agree");
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_sweep_contacts: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_sweep_contacts: null spheres / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_sweep_contacts: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_sweep_contacts: negative sphere count");
-    if (r->max_tris < 0 || r->max_tris > RT_CONTACTS_MAX) return arg_err(ctx, "rt_sweep_contacts: max_tris must be 0..16");
-    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_sweep_contacts: count_all must be 0 or 1");
-    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_sweep_contacts: max_tris = 0 needs count_all");
+    if (int rc = rtq::check_enter(rtq::CONTACTS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::CONTACTS, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && (!r->centre || !r->motion || !r->radius))
         return arg_err(ctx, "rt_sweep_contacts: null centre / motion / radius");
     if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->t && !out->point)
         return arg_err(ctx, "rt_sweep_contacts: max_tris > 0 needs a tri, a t or a point output");
-    if (r->n > 0 && r->max_tris == 0 && !out->count)
-        return arg_err(ctx, "rt_sweep_contacts: a counting query needs a count output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::CT_NCOUNT + 1);
-    if (!ctx->d_ctq) HIPC(hipMalloc((void**)&ctx->d_ctq, cbytes));
-    if (!ctx->c_ev0) HIPC(hipEventCreate(&ctx->c_ev0));
-    if (!ctx->c_ev1) HIPC(hipEventCreate(&ctx->c_ev1));
-    HIPC(hipMemsetAsync(ctx->d_ctq, 0, cbytes, ctx->stream));
-    ctx->contacts_run = true;
-    ctx->c_launched = false;
+    if (int rc = rtq::check_count_out(rtq::CONTACTS, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
+    rtd::CArgs A;
+    if (int rc = query_begin(ctx, rtq::CONTACTS, rtd::CT_NCOUNT, A)) return rc;
     if (r->n == 0) return RT_OK;
     const bool want_p = r->max_tris > 0 && out->point;
-    if (want_p && !ctx->d_ref_inv) {  // original index -> the reference tree's record (rt_neighbours.hpp ref_inv)
-        const int nt = ctx->n_tris;
-        HIPC(hipMalloc((void**)&ctx->d_ref_inv, sizeof(int) * (size_t)std::max(nt, 1)));
-        HIPC(hipMemsetAsync(ctx->d_ref_inv, 0, sizeof(int) * (size_t)std::max(nt, 1), ctx->stream));
-        if (nt > 0) {
-            rtd::k_invert_orig<<<(nt + 255) / 256, 256, 0, ctx->stream>>>(ctx->ref.orig, nt, ctx->d_ref_inv);
-            HIPC(hipGetLastError());
-        }
-    }
-    rtd::CArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (want_p)
+        if (int rc = ensure_ref_inv(ctx)) return rc;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.centre = r->centre;
     A.motion = r->motion;
@@ -3695,36 +3394,17 @@ extern "C" int rt_sweep_contacts(rt_ctx* ctx, const rt_sphere_contacts* r, const
     A.out = want_p ? out->point : nullptr;
     A.count = out->count;
     A.ref_inv = ctx->d_ref_inv;
-    A.counters = ctx->d_ctq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_ctq + rtd::CT_NCOUNT);
     A.n = r->n;
     A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::sweep_domain
     A.max_tris = r->max_tris;
     A.count_all = r->count_all;
-    const CFn k = contacts_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->c_resident.find((const void*)k);
-    if (res == ctx->c_resident.end()) res = ctx->c_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->c_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->c_ev1, ctx->stream));
-    ctx->c_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::CONTACTS, FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_contacts),
+                        A);
 }
 
 extern "C" int rt_get_contacts_info(rt_ctx* ctx, rt_contacts_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->contacts_run) {
-        ctx->err = "rt_get_contacts_info: no contacts query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::CT_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_ctq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::CONTACTS, "rt_get_contacts_info: no contacts query run", c, info)) return rc;
     info->spheres = (long long)c[rtd::CT_SPHERES];
     info->found = (long long)c[rtd::CT_FOUND];
     info->tris_stored = (long long)c[rtd::CT_STORED];
@@ -3735,61 +3415,26 @@ extern "C" int rt_get_contacts_info(rt_ctx* ctx, rt_contacts_info* info) {
     info->nodes_visited = (long long)c[rtd::CT_NODES];
     info->tris_tested = (long long)c[rtd::CT_TRIS];
     info->stack_overflows = (long long)c[rtd::CT_ERR];
-    if (ctx->c_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->c_ev0, ctx->c_ev1));
-    if (c[rtd::CT_ERR]) {
-        ctx->err = "rt_get_contacts_info: the query's traversal stack overflowed " + std::to_string(c[rtd::CT_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::CONTACTS, "rt_get_contacts_info", c[rtd::CT_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- cut queries (rt_cut.hpp)
-namespace {
-using XFn = void (*)(rtd::XArgs);
-// the smallest list capacity that holds max_tris (0: the counting build)
-XFn cut_kernel(int max_tris, bool strict) {
-    using rtd::k_cut;
-    if (max_tris == 0) return strict ? k_cut<0, true> : k_cut<0, false>;
-    if (max_tris <= 4) return strict ? k_cut<4, true> : k_cut<4, false>;
-    if (max_tris <= 8) return strict ? k_cut<8, true> : k_cut<8, false>;
-    return strict ? k_cut<16, true> : k_cut<16, false>;
-}
-}  // namespace
-
 extern "C" int rt_cut_triangles(rt_ctx* ctx, const rt_tris* r, const rt_cut_results* out) {
     static_assert(RT_CUTS_MAX == rtd::CUTS_MAX && rtd::CUTS_MAX == rtd::OVERLAPS_MAX,
                   "rt_hip.h, rt_cut.hpp and the capacities of rt_overlap.hpp's OState must agree");
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_cut_triangles: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_cut_triangles: null tris / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST) return arg_err(ctx, "rt_cut_triangles: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_cut_triangles: negative triangle count");
-    if (r->max_tris < 0 || r->max_tris > RT_CUTS_MAX) return arg_err(ctx, "rt_cut_triangles: max_tris must be 0..16");
-    if (r->count_all != 0 && r->count_all != 1) return arg_err(ctx, "rt_cut_triangles: count_all must be 0 or 1");
-    if (r->max_tris == 0 && !r->count_all) return arg_err(ctx, "rt_cut_triangles: max_tris = 0 needs count_all");
+    if (int rc = rtq::check_enter(rtq::CUTS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::CUTS, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
     if ((r->offsets != nullptr) != (out->list != nullptr))
         return arg_err(ctx, "rt_cut_triangles: offsets and list are given together or not at all");
     if (out->list_seg && !out->list) return arg_err(ctx, "rt_cut_triangles: list_seg needs a list");
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && !r->tris) return arg_err(ctx, "rt_cut_triangles: null tris");
     if (r->n > 0 && r->max_tris > 0 && !out->tri) return arg_err(ctx, "rt_cut_triangles: max_tris > 0 needs a tri output");
-    if (r->n > 0 && r->max_tris == 0 && !out->count)
-        return arg_err(ctx, "rt_cut_triangles: a counting query needs a count output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::X_NCOUNT + 1);
-    if (!ctx->d_cutq) HIPC(hipMalloc((void**)&ctx->d_cutq, cbytes));
-    if (!ctx->x_ev0) HIPC(hipEventCreate(&ctx->x_ev0));
-    if (!ctx->x_ev1) HIPC(hipEventCreate(&ctx->x_ev1));
-    HIPC(hipMemsetAsync(ctx->d_cutq, 0, cbytes, ctx->stream));
-    ctx->cuts_run = true;
-    ctx->x_launched = false;
-    if (r->n == 0) return RT_OK;
+    if (int rc = rtq::check_count_out(rtq::CUTS, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
     rtd::XArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::CUTS, rtd::X_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.tris = r->tris;
     A.offsets = r->offsets;
@@ -3797,35 +3442,15 @@ extern "C" int rt_cut_triangles(rt_ctx* ctx, const rt_tris* r, const rt_cut_resu
     A.count = out->count;
     A.list = out->list;
     A.list_seg = out->list_seg;
-    A.counters = ctx->d_cutq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_cutq + rtd::X_NCOUNT);
     A.n = r->n;
     A.max_tris = r->max_tris;
     A.count_all = r->count_all;
-    const XFn k = cut_kernel(r->max_tris, r->kernel == RT_KERNEL_STRICT);
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->x_resident.find((const void*)k);
-    if (res == ctx->x_resident.end()) res = ctx->x_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->x_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->x_ev1, ctx->stream));
-    ctx->x_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::CUTS, FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_cut), A);
 }
 
 extern "C" int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->cuts_run) {
-        ctx->err = "rt_get_cuts_info: no cut query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::X_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_cutq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::CUTS, "rt_get_cuts_info: no cut query run", c, info)) return rc;
     info->triangles = (long long)c[rtd::X_TRIS];
     info->found = (long long)c[rtd::X_FOUND];
     info->stored = (long long)c[rtd::X_STORED];
@@ -3837,41 +3462,21 @@ extern "C" int rt_get_cuts_info(rt_ctx* ctx, rt_cuts_info* info) {
     info->nodes_visited = (long long)c[rtd::X_NODES];
     info->pairs_tested = (long long)c[rtd::X_PAIRS];
     info->stack_overflows = (long long)c[rtd::X_ERR];
-    if (ctx->x_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->x_ev0, ctx->x_ev1));
-    if (c[rtd::X_ERR]) {
-        ctx->err = "rt_get_cuts_info: the query's traversal stack overflowed " + std::to_string(c[rtd::X_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::CUTS, "rt_get_cuts_info", c[rtd::X_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 // ---------------------------------------------------------------- clearance queries (rt_clearance.hpp)
 extern "C" int rt_clearance_triangles(rt_ctx* ctx, const rt_clear_tris* r, const rt_clearance_results* out) {
     if (!ctx) return RT_E_ARG;
-    if (!ctx->has_scene) {
-        ctx->err = "rt_clearance_triangles: no scene uploaded";
-        return RT_E_STATE;
-    }
-    if (!r || !out) return arg_err(ctx, "rt_clearance_triangles: null tris / results");
-    if (r->kernel < RT_KERNEL_AUTO || r->kernel > RT_KERNEL_FAST)
-        return arg_err(ctx, "rt_clearance_triangles: bad kernel");
-    if (r->n < 0) return arg_err(ctx, "rt_clearance_triangles: negative triangle count");
+    if (int rc = rtq::check_enter(rtq::CLEARANCE, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::CLEARANCE, r->kernel, r->n, ctx->err)) return rc;
     // (n = 0 reads and writes nothing: empty arrays may have no address)
     if (r->n > 0 && !r->tris) return arg_err(ctx, "rt_clearance_triangles: null tris");
     if (r->n > 0 && !out->tri && !out->d2 && !out->on_query && !out->on_mesh && !out->kind)
         return arg_err(ctx, "rt_clearance_triangles: needs a tri, a d2, an on_query, an on_mesh or a kind output");
-    HIPC(hipSetDevice(ctx->device));
-    const size_t cbytes = sizeof(unsigned long long) * (rtd::CL_NCOUNT + 1);
-    if (!ctx->d_clq) HIPC(hipMalloc((void**)&ctx->d_clq, cbytes));
-    if (!ctx->l_ev0) HIPC(hipEventCreate(&ctx->l_ev0));
-    if (!ctx->l_ev1) HIPC(hipEventCreate(&ctx->l_ev1));
-    HIPC(hipMemsetAsync(ctx->d_clq, 0, cbytes, ctx->stream));
-    ctx->clearance_run = true;
-    ctx->l_launched = false;
-    if (r->n == 0) return RT_OK;
     rtd::CLArgs A;
-    std::memset(&A, 0, sizeof A);
+    if (int rc = query_begin(ctx, rtq::CLEARANCE, rtd::CL_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
     A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
     A.tris = r->tris;
     A.max_dist2 = r->max_dist2;
@@ -3880,33 +3485,14 @@ extern "C" int rt_clearance_triangles(rt_ctx* ctx, const rt_clear_tris* r, const
     A.on_query = out->on_query;
     A.on_mesh = out->on_mesh;
     A.kind = out->kind;
-    A.counters = ctx->d_clq;
-    A.work = reinterpret_cast<unsigned int*>(ctx->d_clq + rtd::CL_NCOUNT);
     A.n = r->n;
     void (*k)(rtd::CLArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_clearance<true> : rtd::k_clearance<false>;
-    const int chunks = (int)(((long long)r->n + rtd::QUERY_CHUNK - 1) / rtd::QUERY_CHUNK);
-    auto res = ctx->l_resident.find((const void*)k);
-    if (res == ctx->l_resident.end()) res = ctx->l_resident.emplace((const void*)k, resident(k, ctx->device)).first;
-    const int blocks = std::max(1, std::min(res->second, (chunks + 3) / 4));
-    HIPC(hipEventRecord(ctx->l_ev0, ctx->stream));
-    k<<<blocks, rtd::BLOCK, 0, ctx->stream>>>(A);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(ctx->l_ev1, ctx->stream));
-    ctx->l_launched = true;
-    return RT_OK;
+    return query_launch(ctx, rtq::CLEARANCE, k, A);
 }
 
 extern "C" int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info) {
-    if (!ctx || !info) return RT_E_ARG;
-    if (!ctx->clearance_run) {
-        ctx->err = "rt_get_clearance_info: no clearance query run";
-        return RT_E_STATE;
-    }
-    HIPC(hipSetDevice(ctx->device));
-    HIPC(hipStreamSynchronize(ctx->stream));
     unsigned long long c[rtd::CL_NCOUNT];
-    HIPC(hipMemcpy(c, ctx->d_clq, sizeof c, hipMemcpyDeviceToHost));
-    std::memset(info, 0, sizeof *info);
+    if (int rc = query_read(ctx, rtq::CLEARANCE, "rt_get_clearance_info: no clearance query run", c, info)) return rc;
     info->triangles = (long long)c[rtd::CL_TRIS];
     info->found = (long long)c[rtd::CL_FOUND];
     info->walked = (long long)c[rtd::CL_WALKED];
@@ -3916,13 +3502,7 @@ extern "C" int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info) {
     info->pairs_gated = (long long)c[rtd::CL_GATED];
     info->pairs_tested = (long long)c[rtd::CL_PAIRS];
     info->stack_overflows = (long long)c[rtd::CL_ERR];
-    if (ctx->l_launched) HIPC(hipEventElapsedTime(&info->kernel_ms, ctx->l_ev0, ctx->l_ev1));
-    if (c[rtd::CL_ERR]) {
-        ctx->err = "rt_get_clearance_info: the query's traversal stack overflowed " + std::to_string(c[rtd::CL_ERR]) +
-                   " times (wide view deeper than the walk's stack): its results are not valid";
-        return RT_E_KERNEL;
-    }
-    return RT_OK;
+    return query_finish(ctx, rtq::CLEARANCE, "rt_get_clearance_info", c[rtd::CL_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 namespace {
@@ -4781,42 +4361,17 @@ extern "C" void rt_destroy(rt_ctx* ctx) {
                     (void*)ctx->d_full_bgra})
         if (p) (void)hipFree(p);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
-    if (ctx->d_query) (void)hipFree(ctx->d_query);
-    if (ctx->q_ev0) (void)hipEventDestroy(ctx->q_ev0);
-    if (ctx->q_ev1) (void)hipEventDestroy(ctx->q_ev1);
+    for (rt_ctx::QuerySlot& q : ctx->slots) {
+        if (q.counters) (void)hipFree(q.counters);
+        if (q.ev0) (void)hipEventDestroy(q.ev0);
+        if (q.ev1) (void)hipEventDestroy(q.ev1);
+    }
     for (void* p : {(void*)ctx->d_plan, (void*)ctx->d_area})
         if (p) (void)hipFree(p);
     if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
     if (ctx->h_lights) (void)hipHostFree(ctx->h_lights);
     for (hipEvent_t e : {ctx->u_ev0, ctx->u_ev1, ctx->u_evs, ctx->lights_ev, ctx->r_ev0, ctx->r_ev1, ctx->r_evs})
         if (e) (void)hipEventDestroy(e);
-    if (ctx->d_shq) (void)hipFree(ctx->d_shq);
-    if (ctx->s_ev0) (void)hipEventDestroy(ctx->s_ev0);
-    if (ctx->s_ev1) (void)hipEventDestroy(ctx->s_ev1);
-    if (ctx->d_hitq) (void)hipFree(ctx->d_hitq);
-    if (ctx->h_ev0) (void)hipEventDestroy(ctx->h_ev0);
-    if (ctx->h_ev1) (void)hipEventDestroy(ctx->h_ev1);
-    if (ctx->d_nearq) (void)hipFree(ctx->d_nearq);
-    if (ctx->n_ev0) (void)hipEventDestroy(ctx->n_ev0);
-    if (ctx->n_ev1) (void)hipEventDestroy(ctx->n_ev1);
-    if (ctx->d_nbq) (void)hipFree(ctx->d_nbq);
-    if (ctx->b_ev0) (void)hipEventDestroy(ctx->b_ev0);
-    if (ctx->b_ev1) (void)hipEventDestroy(ctx->b_ev1);
-    if (ctx->d_ovq) (void)hipFree(ctx->d_ovq);
-    if (ctx->o_ev0) (void)hipEventDestroy(ctx->o_ev0);
-    if (ctx->o_ev1) (void)hipEventDestroy(ctx->o_ev1);
-    if (ctx->d_swq) (void)hipFree(ctx->d_swq);
-    if (ctx->w_ev0) (void)hipEventDestroy(ctx->w_ev0);
-    if (ctx->w_ev1) (void)hipEventDestroy(ctx->w_ev1);
-    if (ctx->d_ctq) (void)hipFree(ctx->d_ctq);
-    if (ctx->c_ev0) (void)hipEventDestroy(ctx->c_ev0);
-    if (ctx->c_ev1) (void)hipEventDestroy(ctx->c_ev1);
-    if (ctx->d_cutq) (void)hipFree(ctx->d_cutq);
-    if (ctx->x_ev0) (void)hipEventDestroy(ctx->x_ev0);
-    if (ctx->x_ev1) (void)hipEventDestroy(ctx->x_ev1);
-    if (ctx->d_clq) (void)hipFree(ctx->d_clq);
-    if (ctx->l_ev0) (void)hipEventDestroy(ctx->l_ev0);
-    if (ctx->l_ev1) (void)hipEventDestroy(ctx->l_ev1);
     for (int i = 0; i < rt_ctx::NEV; i++) {
         if (ctx->ev0s[i]) (void)hipEventDestroy(ctx->ev0s[i]);
         if (ctx->ev1s[i]) (void)hipEventDestroy(ctx->ev1s[i]);

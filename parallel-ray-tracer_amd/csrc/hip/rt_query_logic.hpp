@@ -1,0 +1,81 @@
+// rt_query_logic.hpp — what the ten query entry points (rt_trace_rays ... rt_clearance_triangles, rt_hip.hip) decide
+// alike, kept free of HIP so that tests/c/query_logic_test.cpp can check it with g++ alone:
+//   * Fam / FAMILY: the families, and the words in which their messages differ;
+//   * check_enter, check_args, check_count_out: the argument checks all of them make, with their messages;
+//   * list_capacity: the list families' kernel capacity for a max_hits / max_tris;
+//   * grid_blocks: the persistent grid of a query launch.
+// A check that one family alone makes stays in its entry point; allocating and launching stay in rt_hip.hip.
+#pragma once
+#include <algorithm>
+#include <string>
+
+#include "rt_hip.h"
+
+namespace rtq {
+
+enum Fam { RAYS, SHADE, HITS, NEAREST, NEIGHBOURS, OVERLAPS, SWEEP, CONTACTS, CUTS, CLEARANCE, NFAM };
+
+struct Family {
+    const char* fn;     // the entry point, as its messages begin
+    const char* items;  // what it is given ("null <items> / results")
+    const char* noun;   // what n counts ("negative <noun> count")
+    const char* cap;    // the list families' capacity field; null: the family has no lists
+};
+constexpr Family FAMILY[NFAM] = {
+    {"rt_trace_rays", "rays", "ray", nullptr},
+    {"rt_shade_rays", "rays", "ray", nullptr},
+    {"rt_trace_hits", "rays", "ray", "max_hits"},
+    {"rt_nearest_points", "points", "point", nullptr},
+    {"rt_nearest_tris", "points", "point", "max_tris"},
+    {"rt_overlap_boxes", "boxes", "box", "max_tris"},
+    {"rt_sweep_spheres", "spheres", "sphere", nullptr},
+    {"rt_sweep_contacts", "spheres", "sphere", "max_tris"},
+    {"rt_cut_triangles", "tris", "triangle", "max_tris"},
+    {"rt_clearance_triangles", "tris", "triangle", nullptr},
+};
+
+constexpr int LIST_MAX = 16;  // RT_HITS_MAX, RT_NEIGHBOURS_MAX, ... (rt_hip.hip asserts each)
+
+// Every check returns RT_OK, or the call's status with its message in err (untouched otherwise).
+inline int refuse(int rc, Fam f, const std::string& what, std::string& err) {
+    err = std::string(FAMILY[f].fn) + ": " + what;
+    return rc;
+}
+
+// the first checks of an entry point: a scene, and both argument structs
+inline int check_enter(Fam f, bool has_scene, bool have_args, std::string& err) {
+    if (!has_scene) return refuse(RT_E_STATE, f, "no scene uploaded", err);
+    if (!have_args) return refuse(RT_E_ARG, f, std::string("null ") + FAMILY[f].items + " / results", err);
+    return RT_OK;
+}
+
+// kernel and n; for a list family also its capacity (Family::cap names the field) and count_all
+inline int check_args(Fam f, int kernel, int n, int cap, int count_all, std::string& err) {
+    if (kernel < RT_KERNEL_AUTO || kernel > RT_KERNEL_FAST) return refuse(RT_E_ARG, f, "bad kernel", err);
+    if (n < 0) return refuse(RT_E_ARG, f, std::string("negative ") + FAMILY[f].noun + " count", err);
+    const char* field = FAMILY[f].cap;
+    if (!field) return RT_OK;
+    if (cap < 0 || cap > LIST_MAX) return refuse(RT_E_ARG, f, std::string(field) + " must be 0..16", err);
+    if (count_all != 0 && count_all != 1) return refuse(RT_E_ARG, f, "count_all must be 0 or 1", err);
+    if (cap == 0 && !count_all) return refuse(RT_E_ARG, f, std::string(field) + " = 0 needs count_all", err);
+    return RT_OK;
+}
+inline int check_args(Fam f, int kernel, int n, std::string& err) { return check_args(f, kernel, n, 0, 1, err); }
+
+// a list family's last check: a query that only counts writes counts
+inline int check_count_out(Fam f, int n, int cap, bool has_count, std::string& err) {
+    if (n > 0 && cap == 0 && !has_count) return refuse(RT_E_ARG, f, "a counting query needs a count output", err);
+    return RT_OK;
+}
+
+// the smallest list capacity a kernel is built for that holds cap entries (0: the counting build)
+constexpr int list_capacity(int cap) { return cap == 0 ? 0 : cap <= 4 ? 4 : cap <= 8 ? 8 : 16; }
+
+// workgroups of a query launch: persistent ones that take chunks of `chunk` queries from a counter, four chunks per
+// workgroup while that leaves some of the `resident` ones idle
+inline int grid_blocks(int n, int chunk, int resident) {
+    const int chunks = (int)(((long long)n + chunk - 1) / chunk);
+    return std::max(1, std::min(resident, (chunks + 3) / 4));
+}
+
+}  // namespace rtq

@@ -362,6 +362,38 @@ class Renderer:
         f32 = (torch.float32,)
         return _ptr(origins, "origins", 3 * n, f32, self.device), _ptr(dirs, "dirs", 3 * n, f32, self.device), n
 
+    def _points(self, points, max_dist2, point, tail):
+        """(points pointer, max_dist2 pointer or None, n) of a nearest / nearest_tris call: points a [n, 3] float32
+        contiguous tensor on this device or a raw (pointer, n), max_dist2 an optional [n] float32 tensor; the caller's
+        `point` output, when a tensor, has the shape [n, *tail]. Shapes are checked before devices and dtypes."""
+        import torch
+        f32 = (torch.float32,)
+        if isinstance(points, tuple):  # a raw pointer: (pointer, n)
+            pp, n = points
+            if not isinstance(pp, int) or not isinstance(n, int) or n < 0:
+                raise RtError("points: a raw pointer is given as points=(pointer, n)")
+        else:
+            if not isinstance(points, torch.Tensor):
+                raise RtError(f"points: expected a torch tensor or a raw (pointer, n), got {type(points).__name__}")
+            if points.dim() != 2 or points.shape[1] != 3:
+                raise RtError(f"points: shape {tuple(points.shape)}, expected [n, 3]")
+            n = points.shape[0]
+        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
+            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
+        if isinstance(point, torch.Tensor) and (point.dim() != 1 + len(tail) or tuple(point.shape[1:]) != tail):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, {', '.join(map(str, tail))}]")
+        if not isinstance(points, tuple):
+            pp = _ptr(points, "points", 3 * n, f32, self.device)
+        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
+            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
+        return pp, _ptr(max_dist2, "max_dist2", n, f32, self.device), n
+
+    def _info(self, struct, fn):
+        """the counters a rt_get_*_info call fills, as a dict (the call synchronises and raises on an overflowed stack)"""
+        i = struct()
+        self._chk(getattr(_L, fn)(self._ctx, ctypes.byref(i)), fn)
+        return {f: getattr(i, f) for f, _ in struct._fields_}
+
     def _trace(self, rays, res):
         self._chk(_L.rt_trace_rays(self._ctx, ctypes.byref(rays), ctypes.byref(res)), "rt_trace_rays")
 
@@ -403,9 +435,7 @@ class Renderer:
     def query_info(self):
         """rt_get_query_info: the last query's counters (rays, hits, the rays each view served, strict_rays outside
         the fast walk's domain, tie_rewalks) and kernel_ms; synchronises; raises when the query overflowed a stack"""
-        i = _lib.QueryInfo()
-        self._chk(_L.rt_get_query_info(self._ctx, ctypes.byref(i)), "rt_get_query_info")
-        return {f: getattr(i, f) for f, _ in _lib.QueryInfo._fields_}
+        return self._info(_lib.QueryInfo, "rt_get_query_info")
 
     def shade_rays(self, origins, dirs, bounces=4, kernel="auto", regroup=0, unclamped=False, rgb=None, bgra=None,
                    hit=None, t=None, bounce_hit=None):
@@ -436,9 +466,7 @@ class Renderer:
         """rt_get_shade_info: the last shade query's counters (rays, hits, reflection, shadow, shadow_skipped as
         stats() counts a frame's; strict_paths outside the fast walks' domain; tie_rewalks) and kernel_ms;
         synchronises; raises when the query overflowed a stack"""
-        i = _lib.ShadeInfo()
-        self._chk(_L.rt_get_shade_info(self._ctx, ctypes.byref(i)), "rt_get_shade_info")
-        return {f: getattr(i, f) for f, _ in _lib.ShadeInfo._fields_}
+        return self._info(_lib.ShadeInfo, "rt_get_shade_info")
 
     def trace_hits(self, origins, dirs, max_hits=8, t_max=None, count_all=False, kernel="auto", tri=None, t=None,
                    count=None):
@@ -480,9 +508,7 @@ class Renderer:
         """rt_get_hits_info: the last hits query's counters (rays, rays_hit, hits_stored, hits_counted, the rays each
         view served, exhaustive_rays tested against every triangle) and kernel_ms; synchronises; raises when the query
         overflowed a stack"""
-        i = _lib.HitsInfo()
-        self._chk(_L.rt_get_hits_info(self._ctx, ctypes.byref(i)), "rt_get_hits_info")
-        return {f: getattr(i, f) for f, _ in _lib.HitsInfo._fields_}
+        return self._info(_lib.HitsInfo, "rt_get_hits_info")
 
     def nearest(self, points, max_dist2=None, kernel="auto", tri=None, d2=None, point=None):
         """rt_nearest_points: per point the nearest triangle of the scene, the squared distance to it and the closest
@@ -496,25 +522,7 @@ class Renderer:
         renderer's stream: sync() or nearest_info() before the results are read on another stream."""
         import torch
         f32, i32 = (torch.float32,), (torch.int32,)
-        if isinstance(points, tuple):  # a raw pointer: (pointer, n)
-            pp, n = points
-            if not isinstance(pp, int) or not isinstance(n, int) or n < 0:
-                raise RtError("points: a raw pointer is given as points=(pointer, n)")
-        else:
-            if not isinstance(points, torch.Tensor):
-                raise RtError(f"points: expected a torch tensor or a raw (pointer, n), got {type(points).__name__}")
-            if points.dim() != 2 or points.shape[1] != 3:
-                raise RtError(f"points: shape {tuple(points.shape)}, expected [n, 3]")
-            n = points.shape[0]
-        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
-            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
-        if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
-            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
-        if not isinstance(points, tuple):
-            pp = _ptr(points, "points", 3 * n, f32, self.device)
-        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
-            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
-        pm = _ptr(max_dist2, "max_dist2", n, f32, self.device)
+        pp, pm, n = self._points(points, max_dist2, point, (3,))
         for x, what, k, dt in ((tri, "tri", n, i32), (d2, "d2", n, f32), (point, "point", 3 * n, f32)):
             _ptr(x, what, k, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
         dev = f"cuda:{self.device}"
@@ -534,9 +542,7 @@ class Renderer:
         """rt_get_nearest_info: the last nearest query's counters (points, found, walked_points, exhaustive_points,
         empty_points, nodes_visited, tris_tested) and kernel_ms; synchronises; raises when the query overflowed its
         stack"""
-        i = _lib.NearestInfo()
-        self._chk(_L.rt_get_nearest_info(self._ctx, ctypes.byref(i)), "rt_get_nearest_info")
-        return {f: getattr(i, f) for f, _ in _lib.NearestInfo._fields_}
+        return self._info(_lib.NearestInfo, "rt_get_nearest_info")
 
     def nearest_tris(self, points, k=8, max_dist2=None, count_all=False, points_out=False, kernel="auto", tri=None,
                      d2=None, count=None, point=None):
@@ -556,25 +562,7 @@ class Renderer:
             raise RtError(f"k: {k!r}, expected an int in 0..{_lib.NEIGHBOURS_MAX}")
         if k == 0 and not count_all:
             raise RtError("k = 0 stores nothing: it needs count_all=True")
-        if isinstance(points, tuple):  # a raw pointer: (pointer, n)
-            pp, n = points
-            if not isinstance(pp, int) or not isinstance(n, int) or n < 0:
-                raise RtError("points: a raw pointer is given as points=(pointer, n)")
-        else:
-            if not isinstance(points, torch.Tensor):
-                raise RtError(f"points: expected a torch tensor or a raw (pointer, n), got {type(points).__name__}")
-            if points.dim() != 2 or points.shape[1] != 3:
-                raise RtError(f"points: shape {tuple(points.shape)}, expected [n, 3]")
-            n = points.shape[0]
-        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
-            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
-        if isinstance(point, torch.Tensor) and (point.dim() != 3 or tuple(point.shape[1:]) != (k, 3)):
-            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, {k}, 3]")
-        if not isinstance(points, tuple):
-            pp = _ptr(points, "points", 3 * n, f32, self.device)
-        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
-            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
-        pm = _ptr(max_dist2, "max_dist2", n, f32, self.device)
+        pp, pm, n = self._points(points, max_dist2, point, (k, 3))
         for x, what, m, dt in ((tri, "tri", n * k, i32), (d2, "d2", n * k, f32), (count, "count", n, i32),
                                (point, "point", 3 * n * k, f32)):
             _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
@@ -599,9 +587,7 @@ class Renderer:
         """rt_get_neighbours_info: the last neighbours query's counters (points, found, tris_stored, tris_counted,
         walked_points, exhaustive_points, empty_points, nodes_visited, tris_tested) and kernel_ms; synchronises; raises
         when the query overflowed its stack"""
-        i = _lib.NeighboursInfo()
-        self._chk(_L.rt_get_neighbours_info(self._ctx, ctypes.byref(i)), "rt_get_neighbours_info")
-        return {f: getattr(i, f) for f, _ in _lib.NeighboursInfo._fields_}
+        return self._info(_lib.NeighboursInfo, "rt_get_neighbours_info")
 
     def _boxes(self, lo, hi):
         """(lo pointer, hi pointer, n) of two [n, 3] float32 contiguous tensors on this device, or of raw pointers
@@ -658,9 +644,7 @@ class Renderer:
         """rt_get_overlaps_info: the last overlap query's counters (boxes, found, tris_stored, tris_counted,
         tris_listed, walked_boxes, exhaustive_boxes, empty_boxes, nodes_visited, tris_tested) and kernel_ms;
         synchronises; raises when the query overflowed its stack"""
-        i = _lib.OverlapsInfo()
-        self._chk(_L.rt_get_overlaps_info(self._ctx, ctypes.byref(i)), "rt_get_overlaps_info")
-        return {f: getattr(i, f) for f, _ in _lib.OverlapsInfo._fields_}
+        return self._info(_lib.OverlapsInfo, "rt_get_overlaps_info")
 
     @staticmethod
     def _spheres(centres, motions, radius, t_max):
@@ -743,9 +727,7 @@ class Renderer:
         """rt_get_sweep_info: the last sweep query's counters (spheres, found, empty_spheres, walked_spheres,
         exhaustive_spheres, nodes_visited, tris_tested) and kernel_ms; synchronises; raises when the query overflowed
         its stack"""
-        i = _lib.SweepInfo()
-        self._chk(_L.rt_get_sweep_info(self._ctx, ctypes.byref(i)), "rt_get_sweep_info")
-        return {f: getattr(i, f) for f, _ in _lib.SweepInfo._fields_}
+        return self._info(_lib.SweepInfo, "rt_get_sweep_info")
 
     def sweep_contacts(self, centres, motions, radius, k=8, t_max=None, count_all=False, points_out=False,
                        kernel="auto", tri=None, t=None, count=None, point=None):
@@ -803,9 +785,7 @@ class Renderer:
         """rt_get_contacts_info: the last contacts query's counters (spheres, found, tris_stored, tris_counted,
         walked_spheres, exhaustive_spheres, empty_spheres, nodes_visited, tris_tested) and kernel_ms; synchronises;
         raises when the query overflowed its stack"""
-        i = _lib.ContactsInfo()
-        self._chk(_L.rt_get_contacts_info(self._ctx, ctypes.byref(i)), "rt_get_contacts_info")
-        return {f: getattr(i, f) for f, _ in _lib.ContactsInfo._fields_}
+        return self._info(_lib.ContactsInfo, "rt_get_contacts_info")
 
     def overlaps_csr(self, lo, hi, kernel="auto"):
         """every box's full S_i, in index order -> (offsets [n + 1] int32, tris [offsets[n]] int32): box i's triangles
@@ -891,9 +871,7 @@ class Renderer:
         """rt_get_cuts_info: the last cut query's counters (triangles, found, stored, counted, listed, walked,
         exhaustive, empty, nodes_visited, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed
         its stack"""
-        i = _lib.CutsInfo()
-        self._chk(_L.rt_get_cuts_info(self._ctx, ctypes.byref(i)), "rt_get_cuts_info")
-        return {f: getattr(i, f) for f, _ in _lib.CutsInfo._fields_}
+        return self._info(_lib.CutsInfo, "rt_get_cuts_info")
 
     def cuts_csr(self, tris, segments=True, kernel="auto"):
         """every query triangle's full S_i, in index order, with the cut segments -> (offsets [n + 1] int32, tri
@@ -980,9 +958,7 @@ class Renderer:
         """rt_get_clearance_info: the last clearance query's counters (triangles, found, walked, exhaustive, empty,
         nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed its
         stack"""
-        i = _lib.ClearanceInfo()
-        self._chk(_L.rt_get_clearance_info(self._ctx, ctypes.byref(i)), "rt_get_clearance_info")
-        return {f: getattr(i, f) for f, _ in _lib.ClearanceInfo._fields_}
+        return self._info(_lib.ClearanceInfo, "rt_get_clearance_info")
 
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
@@ -1003,9 +979,7 @@ class Renderer:
         """rt_get_update_info: what the last update_vertices did (views refitted / rebuilt, the triangles that joined
         the unit and the primary view, the new scene magnitude, the full view's area_ratio against its build) and
         update_ms; synchronises"""
-        i = _lib.UpdateInfo()
-        self._chk(_L.rt_get_update_info(self._ctx, ctypes.byref(i)), "rt_get_update_info")
-        return {f: getattr(i, f) for f, _ in _lib.UpdateInfo._fields_}
+        return self._info(_lib.UpdateInfo, "rt_get_update_info")
 
     def rebuild_views(self, coords, mode="auto"):
         """rt_rebuild_views: update_vertices(coords), then new topologies for the fast walk's wide views (full, unit,
