@@ -923,6 +923,90 @@ typedef struct rt_clearance_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info);
 
+/* Proximity queries: per caller-supplied triangle the k nearest mesh triangles, their squared distances and pairs of
+ * closest points, and the number of mesh triangles within a margin -- rt_clearance_triangles' plural form, as
+ * rt_nearest_tris is rt_nearest_points' (every mesh face within a cloth or contact solver's collision margin with the
+ * closest points of each pair, the number of faces closer than a tolerance, the few closest faces of a clash report).
+ * Query i is a triangle q0, q1, q2 with an optional bound max_dist2[i]. Its candidate set is clearance's own, in
+ * clearance's order:
+ *   S_i = { j : D(q, triangle j) <= fminf(max_dist2[i], FLT_MAX) }, ordered by (D ascending, original index ascending).
+ * D, the pair of points and kind are exactly rt_clearance_triangles' sequence above: the fifteen candidates, then the
+ * crossing (kind 15, D = 0, both points the cut segment's first end). D of a pair is a function of the query and the
+ * mesh triangle alone: it depends on no limit a walk holds and on nothing found before it, so a pair has the same bits
+ * in every list, count and segment, under every kernel and view. The plural form relies on that.
+ * S_i is empty, decided before any walk, under clearance's rules: any of the nine numbers non-finite, or max_dist2[i]
+ * NaN or negative. 0 is a valid bound (what touches); max_dist2 NULL or +inf: no bound. No input value is an error.
+ * Results, for max_tris (k) in 0..RT_PROXIMITY_MAX; the slots past |S_i| of query i are its unused slots:
+ *   tri[i][0..k)       the first k entries of S_i                       unused slots: -1
+ *   d2[i][0..k)        their D                                          unused slots: FLT_MAX
+ *   on_query[i][0..k)  each pair's point on the query                   unused slots: q0's own bits
+ *   on_mesh[i][0..k)   each pair's point on the mesh triangle           unused slots: q0's own bits
+ *   kind[i][0..k)      each entry's winning candidate, 0..15            unused slots: -1
+ *   count[i]           min(|S_i|, k), or |S_i| itself with count_all
+ * max_tris = 0 with count_all is the pure count: how many mesh triangles lie within the margin. With count_all the
+ * walk prunes at the query's bound alone; without a bound that is a full traversal.
+ * With max_tris = 1 and no count_all, tri, d2, on_query, on_mesh and kind equal rt_clearance_triangles' bit for bit.
+ * With a bound of 0, S_i contains rt_cut_triangles' S_i for the same triangle. It may hold more -- touching pairs whose
+ * fifteen candidates give exactly 0 -- so the two are not promised equal.
+ * The list form (offsets and list given) follows rt_cut_triangles' rules: list[offsets[i] .. offsets[i+1]) receives
+ * members of S_i until it is full, in no stated order; the rest of the segment is not written, and nothing outside it
+ * is. A member written to list[p] has its D in list_d2[p], its points in list_points[p][0] (on the query) and
+ * list_points[p][1] (on the mesh triangle) and its kind in list_kind[p], where those are given. In the list form the
+ * walk prunes at the query's bound alone, as with count_all, whatever max_tris is.
+ * RT_KERNEL_STRICT tests every query against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * boxes ordered and pruned by their distance to the query box against min(the bound, the k-th D found so far), and
+ * answers with the same bits; a scene without a wide view (RT_ACCEL_REFERENCE) runs the exhaustive loop under either.
+ * A proximity query touches nothing a render or any other query owns. */
+#define RT_PROXIMITY_MAX 16
+typedef struct rt_prox_tris {
+    const float* tris;      /* device, [n][3][3] f32: q0, q1, q2 of every query */
+    const float* max_dist2; /* device, [n] f32, nullable */
+    const int* offsets;     /* device, [n + 1] i32, non-decreasing; nullable: given exactly when
+                               rt_proximity_results.list is */
+    int n;                  /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;           /* 0..RT_PROXIMITY_MAX */
+    int count_all;          /* 0 / 1 */
+    int kernel;             /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_prox_tris;
+typedef struct rt_proximity_results { /* device pointers, all nullable within the rules below */
+    int* tri;           /* [n][max_tris] */
+    float* d2;          /* [n][max_tris] */
+    float* on_query;    /* [n][max_tris][3] */
+    float* on_mesh;     /* [n][max_tris][3] */
+    int* kind;          /* [n][max_tris] */
+    int* count;         /* [n]; required for max_tris = 0 */
+    int* list;          /* [offsets[n]]; given exactly when rt_prox_tris.offsets is */
+    float* list_d2;     /* [offsets[n]]; only with list */
+    float* list_points; /* [offsets[n]][2][3] f32; only with list */
+    int* list_kind;     /* [offsets[n]]; only with list */
+} rt_proximity_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null tris with n > 0, max_tris outside 0..RT_PROXIMITY_MAX, max_tris > 0 with tri, d2,
+ * on_query, on_mesh and kind all NULL, max_tris = 0 without count_all and a count pointer, count_all not 0 / 1, offsets
+ * without list or list without offsets, list_d2, list_points or list_kind without list, an unknown kernel, a negative
+ * n. */
+int rt_proximity_triangles(rt_ctx* ctx, const rt_prox_tris* tris, const rt_proximity_results* out);
+typedef struct rt_proximity_info {
+    long long triangles, found; /* found: query triangles with a non-empty S_i */
+    long long stored, counted;  /* sums of min(|S_i|, max_tris) and of count[i] */
+    long long listed;           /* entries written to list: the sum of min(|S_i|, the segment's length) */
+    long long walked;           /* query triangles that walked the wide view */
+    long long exhaustive;       /* query triangles tested against every triangle: all valid ones under RT_KERNEL_STRICT
+                                   or without a wide view (an invalid one is in neither) */
+    long long empty;            /* triangles - found */
+    long long nodes_visited;    /* wide nodes decoded, summed over the queries (a level popped again counts again) */
+    long long pairs_gated;      /* the walk: triangles of a kept leaf slot skipped because the bound of their own corner
+                                   box exceeded the limit, or because the list was full and their least possible key
+                                   lay beyond its last (pure pruning; 0 in the exhaustive loop) */
+    long long pairs_tested;     /* evaluations of D, summed over the queries (exhaustive: queries x triangles); the
+                                   second evaluation that fills on_query, on_mesh and kind is not counted */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_proximity_info;
+/* counters of the last proximity query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results are
+ * not valid), RT_E_STATE before the first */
+int rt_get_proximity_info(rt_ctx* ctx, rt_proximity_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -44,6 +44,7 @@
 #include "rt_contacts.hpp"
 #include "rt_cut.hpp"
 #include "rt_clearance.hpp"
+#include "rt_proximity.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -230,7 +231,7 @@ struct rt_ctx {
     float4* h_lights = nullptr;  // pinned staging of rt_update_lights, 2 x n_lights (freed with the scene)
     hipEvent_t lights_ev = nullptr;
     float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
-    // the queries (rt_trace_rays ... rt_clearance_triangles): one slot per family (rtq::Fam), so that a query touches
+    // the queries (rt_trace_rays ... rt_proximity_triangles): one slot per family (rtq::Fam), so that a query touches
     // neither a render's state nor another family's info. counters: the family's [NCOUNT] counters, then its chunk
     // counter (made by the family's first query); ev0, ev1: around its last launch; run: a query was accepted (its info
     // can be read); launched: that query had n > 0, so the events were recorded
@@ -238,11 +239,11 @@ struct rt_ctx {
         unsigned long long* counters = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool run = false, launched = false;
-    } slots[rtq::NFAM];
+    } slots[rtq::NFAM_ALL];
     // resident workgroups of each query kernel, by its address (query_resident; 0: a k_shade build that does not fit)
     std::unordered_map<const void*, int> residents;
-    // original triangle index -> position in the reference tree's records (ensure_ref_inv: made by the first neighbour
-    // or contact query of a scene that asks for points, freed with the scene)
+    // original triangle index -> position in the reference tree's records (ensure_ref_inv: made by the first neighbour,
+    // contact or proximity query of a scene that asks for points, freed with the scene)
     int* d_ref_inv = nullptr;
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
@@ -2228,7 +2229,7 @@ int query_read(rt_ctx* ctx, rtq::Fam f, const char* none_run, unsigned long long
 }
 
 // The kernel's time when one was launched, and RT_E_KERNEL when its walks overflowed a stack; too_deep: what was
-// (the three ray families walk every view, the other seven the wide view only).
+// (the three ray families walk every view, the others the wide view only).
 constexpr const char* DEEP_BVH = "BVH deeper than the walks' stacks";
 constexpr const char* DEEP_WIDE = "wide view deeper than the walk's stack";
 int query_finish(rt_ctx* ctx, rtq::Fam f, const char* who, unsigned long long overflows, const char* too_deep,
@@ -3503,6 +3504,69 @@ extern "C" int rt_get_clearance_info(rt_ctx* ctx, rt_clearance_info* info) {
     info->pairs_tested = (long long)c[rtd::CL_PAIRS];
     info->stack_overflows = (long long)c[rtd::CL_ERR];
     return query_finish(ctx, rtq::CLEARANCE, "rt_get_clearance_info", c[rtd::CL_ERR], DEEP_WIDE, &info->kernel_ms);
+}
+
+// ---------------------------------------------------------------- proximity queries (rt_proximity.hpp)
+extern "C" int rt_proximity_triangles(rt_ctx* ctx, const rt_prox_tris* r, const rt_proximity_results* out) {
+    static_assert(RT_PROXIMITY_MAX == rtd::PROXIMITY_MAX && RT_PROXIMITY_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_proximity.hpp and rt_query_logic.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (int rc = rtq::check_enter(rtq::PROXIMITY, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::PROXIMITY, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
+    if ((r->offsets != nullptr) != (out->list != nullptr))
+        return arg_err(ctx, "rt_proximity_triangles: offsets and list are given together or not at all");
+    if ((out->list_d2 || out->list_points || out->list_kind) && !out->list)
+        return arg_err(ctx, "rt_proximity_triangles: list_d2, list_points and list_kind need a list");
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && !r->tris) return arg_err(ctx, "rt_proximity_triangles: null tris");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->d2 && !out->on_query && !out->on_mesh && !out->kind)
+        return arg_err(ctx,
+                       "rt_proximity_triangles: max_tris > 0 needs a tri, a d2, an on_query, an on_mesh or a kind output");
+    if (int rc = rtq::check_count_out(rtq::PROXIMITY, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
+    rtd::PXArgs A;
+    if (int rc = query_begin(ctx, rtq::PROXIMITY, rtd::PX_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
+    const bool lists = r->max_tris > 0;
+    if (lists && (out->on_query || out->on_mesh || out->kind))
+        if (int rc = ensure_ref_inv(ctx)) return rc;
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.tris = r->tris;
+    A.max_dist2 = r->max_dist2;
+    A.offsets = r->offsets;
+    A.tri = lists ? out->tri : nullptr;
+    A.d2 = lists ? out->d2 : nullptr;
+    A.on_query = lists ? out->on_query : nullptr;
+    A.on_mesh = lists ? out->on_mesh : nullptr;
+    A.kind = lists ? out->kind : nullptr;
+    A.count = out->count;
+    A.list = out->list;
+    A.list_d2 = out->list_d2;
+    A.list_points = out->list_points;
+    A.list_kind = out->list_kind;
+    A.ref_inv = ctx->d_ref_inv;
+    A.n = r->n;
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    return query_launch(ctx, rtq::PROXIMITY,
+                        FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_proximity), A);
+}
+
+extern "C" int rt_get_proximity_info(rt_ctx* ctx, rt_proximity_info* info) {
+    unsigned long long c[rtd::PX_NCOUNT];
+    if (int rc = query_read(ctx, rtq::PROXIMITY, "rt_get_proximity_info: no proximity query run", c, info)) return rc;
+    info->triangles = (long long)c[rtd::PX_TRIS];
+    info->found = (long long)c[rtd::PX_FOUND];
+    info->stored = (long long)c[rtd::PX_STORED];
+    info->counted = (long long)c[rtd::PX_COUNTED];
+    info->listed = (long long)c[rtd::PX_LISTED];
+    info->walked = (long long)c[rtd::PX_WALKED];
+    info->exhaustive = (long long)c[rtd::PX_EXH];
+    info->empty = (long long)c[rtd::PX_EMPTY];
+    info->nodes_visited = (long long)c[rtd::PX_NODES];
+    info->pairs_gated = (long long)c[rtd::PX_GATED];
+    info->pairs_tested = (long long)c[rtd::PX_PAIRS];
+    info->stack_overflows = (long long)c[rtd::PX_ERR];
+    return query_finish(ctx, rtq::PROXIMITY, "rt_get_proximity_info", c[rtd::PX_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 namespace {

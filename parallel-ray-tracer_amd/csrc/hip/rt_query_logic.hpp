@@ -1,4 +1,4 @@
-// rt_query_logic.hpp — what the ten query entry points (rt_trace_rays ... rt_clearance_triangles, rt_hip.hip) decide
+// rt_query_logic.hpp — what the query entry points (rt_trace_rays ... rt_proximity_triangles, rt_hip.hip) decide
 // alike, kept free of HIP so that tests/c/query_logic_test.cpp can check it with g++ alone:
 //   * Fam / FAMILY: the families, and the words in which their messages differ;
 //   * check_enter, check_args, check_count_out: the argument checks all of them make, with their messages;
@@ -13,7 +13,11 @@
 
 namespace rtq {
 
-enum Fam { RAYS, SHADE, HITS, NEAREST, NEIGHBOURS, OVERLAPS, SWEEP, CONTACTS, CUTS, CLEARANCE, NFAM };
+// NFAM counts the ten families that tests/c/query_logic_test.cpp tabulates (its EXPECT[rtq::NFAM] has ten rows and its
+// loops run to NFAM), so it keeps the value 10. A family added since is numbered from NFAM upward; NFAM_ALL ends the
+// list and sizes FAMILY and rt_ctx::slots. Each such family's row has a test of its own (tests/c/proximity_logic_test.cpp).
+enum Fam { RAYS, SHADE, HITS, NEAREST, NEIGHBOURS, OVERLAPS, SWEEP, CONTACTS, CUTS, CLEARANCE, NFAM, PROXIMITY = NFAM,
+           NFAM_ALL };
 
 struct Family {
     const char* fn;     // the entry point, as its messages begin
@@ -21,7 +25,7 @@ struct Family {
     const char* noun;   // what n counts ("negative <noun> count")
     const char* cap;    // the list families' capacity field; null: the family has no lists
 };
-constexpr Family FAMILY[NFAM] = {
+constexpr Family FAMILY[NFAM_ALL] = {
     {"rt_trace_rays", "rays", "ray", nullptr},
     {"rt_shade_rays", "rays", "ray", nullptr},
     {"rt_trace_hits", "rays", "ray", "max_hits"},
@@ -32,6 +36,7 @@ constexpr Family FAMILY[NFAM] = {
     {"rt_sweep_contacts", "spheres", "sphere", "max_tris"},
     {"rt_cut_triangles", "tris", "triangle", "max_tris"},
     {"rt_clearance_triangles", "tris", "triangle", nullptr},
+    {"rt_proximity_triangles", "tris", "triangle", "max_tris"},
 };
 
 constexpr int LIST_MAX = 16;  // RT_HITS_MAX, RT_NEIGHBOURS_MAX, ... (rt_hip.hip asserts each)

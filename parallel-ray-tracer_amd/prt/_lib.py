@@ -290,6 +290,29 @@ class ClearanceInfo(ctypes.Structure):  # rt_clearance_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+PROXIMITY_MAX = 16  # RT_PROXIMITY_MAX
+
+
+class ProxTris(ctypes.Structure):  # rt_prox_tris
+    _fields_ = [("tris", ctypes.c_void_p), ("max_dist2", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("n", ctypes.c_int), ("max_tris", ctypes.c_int), ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class ProximityResults(ctypes.Structure):  # rt_proximity_results
+    _fields_ = [("tri", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("on_query", ctypes.c_void_p),
+                ("on_mesh", ctypes.c_void_p), ("kind", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("list", ctypes.c_void_p), ("list_d2", ctypes.c_void_p), ("list_points", ctypes.c_void_p),
+                ("list_kind", ctypes.c_void_p)]
+
+
+class ProximityInfo(ctypes.Structure):  # rt_proximity_info
+    _fields_ = [("triangles", ctypes.c_longlong), ("found", ctypes.c_longlong), ("stored", ctypes.c_longlong),
+                ("counted", ctypes.c_longlong), ("listed", ctypes.c_longlong), ("walked", ctypes.c_longlong),
+                ("exhaustive", ctypes.c_longlong), ("empty", ctypes.c_longlong), ("nodes_visited", ctypes.c_longlong),
+                ("pairs_gated", ctypes.c_longlong), ("pairs_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -425,6 +448,8 @@ def hip():
         L.rt_get_cuts_info.argtypes = [ctypes.c_void_p, P(CutsInfo)]
         L.rt_clearance_triangles.argtypes = [ctypes.c_void_p, P(ClearTris), P(ClearanceResults)]
         L.rt_get_clearance_info.argtypes = [ctypes.c_void_p, P(ClearanceInfo)]
+        L.rt_proximity_triangles.argtypes = [ctypes.c_void_p, P(ProxTris), P(ProximityResults)]
+        L.rt_get_proximity_info.argtypes = [ctypes.c_void_p, P(ProximityInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

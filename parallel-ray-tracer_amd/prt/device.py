@@ -960,6 +960,122 @@ class Renderer:
         stack"""
         return self._info(_lib.ClearanceInfo, "rt_get_clearance_info")
 
+    def _max_dist2(self, max_dist2, n):
+        """the pointer of an optional [n] float32 tensor of squared bounds, checked as clearance checks it"""
+        import torch
+        if isinstance(max_dist2, torch.Tensor) and max_dist2.dim() != 1:
+            raise RtError(f"max_dist2: shape {tuple(max_dist2.shape)}, expected [n]")
+        if max_dist2 is not None and not isinstance(max_dist2, (torch.Tensor, int)):
+            raise RtError(f"max_dist2: expected a torch tensor, got {type(max_dist2).__name__}")
+        return _ptr(max_dist2, "max_dist2", n, (torch.float32,), self.device)
+
+    def proximity(self, tris, k=8, max_dist2=None, count_all=False, pairs_out=False, kernel="auto", tri=None, d2=None,
+                  count=None, on_query=None, on_mesh=None, kind=None):
+        """rt_proximity_triangles: per caller-supplied triangle q0, q1, q2 the k nearest triangles of the scene -- the
+        first k by (D, original triangle index) among those with D <= max_dist2, clearance's own D and order
+        (include/rt_hip.h) -> (tri [n, k] int32, -1 in unused slots; d2 [n, k] float32, FLT_MAX in unused slots; count
+        [n] int32 = min(triangles within the bound, k), or every triangle within the bound with count_all=True, when
+        the walk prunes at the bound only), plus on_query and on_mesh [n, k, 3] float32 (the two points where each pair
+        comes closest; q0's own bits in unused slots) with pairs_out=True or either output given. kind: an optional
+        [n, k] int32 output that receives each entry's winning candidate (0..15; -1 in unused slots). k: 0..16; 0 with
+        count_all=True is a pure count of the triangles within the margin (tri and d2 come back empty). With k = 1 the
+        answer is clearance's, bit for bit. tris, max_dist2 and kernel as clearance takes them; without a bound
+        count_all counts every triangle of the scene, a full traversal. tri / d2 / count / on_query / on_mesh: optional
+        outputs (allocated when not given). proximity_csr gives every query's full set within a bound. Asynchronous on
+        the renderer's stream: sync() or proximity_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.PROXIMITY_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.PROXIMITY_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        pt, n = self._tris(tris)
+        for x, what in ((tri, "tri"), (d2, "d2"), (kind, "kind")):
+            if isinstance(x, torch.Tensor) and (x.dim() != 2 or x.shape[1] != k):
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, k]")
+        for x, what in ((on_query, "on_query"), (on_mesh, "on_mesh")):
+            if isinstance(x, torch.Tensor) and (x.dim() != 3 or tuple(x.shape[1:]) != (k, 3)):
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, k, 3]")
+        pm = self._max_dist2(max_dist2, n)
+        for x, what, m, dt in ((tri, "tri", n * k, i32), (d2, "d2", n * k, f32), (count, "count", n, i32),
+                               (on_query, "on_query", 3 * n * k, f32), (on_mesh, "on_mesh", 3 * n * k, f32),
+                               (kind, "kind", n * k, i32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if d2 is None:
+            d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        pairs = pairs_out or on_query is not None or on_mesh is not None
+        if pairs and on_query is None:
+            on_query = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        if pairs and on_mesh is None:
+            on_mesh = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        res = _lib.ProximityResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                                    _ptr(d2, "d2", n * k, f32, self.device) if k else None,
+                                    _ptr(on_query, "on_query", 3 * n * k, f32, self.device) if k else None,
+                                    _ptr(on_mesh, "on_mesh", 3 * n * k, f32, self.device) if k else None,
+                                    _ptr(kind, "kind", n * k, i32, self.device) if k else None,
+                                    _ptr(count, "count", n, i32, self.device), None, None, None, None)
+        q = _lib.ProxTris(pt, pm, None, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_proximity_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_proximity_triangles")
+        return (tri, d2, count, on_query, on_mesh) if pairs else (tri, d2, count)
+
+    def proximity_info(self):
+        """rt_get_proximity_info: the last proximity query's counters (triangles, found, stored, counted, listed,
+        walked, exhaustive, empty, nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when
+        the query overflowed its stack"""
+        return self._info(_lib.ProximityInfo, "rt_get_proximity_info")
+
+    def proximity_csr(self, tris, max_dist2, pairs=True, kernel="auto"):
+        """every query triangle's full S_i within its bound, in (D, index) order, with the closest points ->
+        (offsets [n + 1] int32, tri [offsets[n]] int32, d2 [offsets[n]] float32, pair [offsets[n], 2, 3] float32; pair
+        is None with pairs=False): the scene's triangles tri[offsets[i]:offsets[i + 1]] lie within max_dist2[i] of
+        query i, nearest first, at d2[p], the pair at p coming closest at pair[p] = (on the query, on the mesh
+        triangle). Two launches of rt_proximity_triangles -- a pure count, then the list form into the counts' prefix
+        sums -- and two sorts that put each segment of the list in (D, index) order, the other arrays permuted
+        alongside. max_dist2: an [n] float32 tensor of squared bounds, as proximity takes it (without one every query
+        lists the whole scene). Synchronises (the total is read on the host); refuses a total of 2^31 or more. tris
+        and kernel as proximity takes them."""
+        import torch
+        pt, n = self._tris(tris)
+        pm = self._max_dist2(max_dist2, n)
+        dev = f"cuda:{self.device}"
+        kern = KERNELS.get(kernel, kernel)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        none = (None,) * 5
+        q = _lib.ProxTris(pt, pm, None, n, 0, 1, kern)
+        res = _lib.ProximityResults(*none, _ptr(count, "count", n, (torch.int32,), self.device), None, None, None, None)
+        self._chk(_L.rt_proximity_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_proximity_triangles")
+        self.proximity_info()  # (synchronises the renderer's stream with torch's; raises on an overflowed stack)
+        ends = torch.cumsum(count, 0, dtype=torch.int64)
+        total = int(ends[-1]) if n else 0
+        if total >= 2 ** 31:
+            raise RtError(f"proximity_csr: {total} entries in all, int32 offsets hold fewer than 2^31: split the "
+                          "triangles or lower the bounds")
+        offsets = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        offsets[1:] = ends.to(torch.int32)
+        idx = torch.empty(total, dtype=torch.int32, device=dev)
+        d2 = torch.empty(total, dtype=torch.float32, device=dev)
+        pair = torch.empty((total, 2, 3), dtype=torch.float32, device=dev) if pairs else None
+        if total == 0:
+            return offsets, idx, d2, pair
+        torch.cuda.current_stream(self.device).synchronize()  # (offsets is torch's work, the query runs on ours)
+        q = _lib.ProxTris(pt, pm, offsets.data_ptr(), n, 0, 1, kern)
+        res = _lib.ProximityResults(*none, count.data_ptr(), idx.data_ptr(), d2.data_ptr(),
+                                    pair.data_ptr() if pairs else None, None)
+        self._chk(_L.rt_proximity_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_proximity_triangles")
+        self.proximity_info()
+        # (row, D, index) does not fit one int64: by D_bits << 32 | index (D >= +0: its bits order as it does), then
+        # stably by row
+        row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), count.to(torch.int64))
+        key = (d2.view(torch.int32).to(torch.int64) << 32) | idx.to(torch.int64)
+        by_key = torch.argsort(key)
+        order = by_key[torch.argsort(row[by_key], stable=True)]
+        return offsets, idx[order], d2[order], pair[order] if pairs else None
+
     def update_vertices(self, coords):
         """rt_update_vertices: every view of the uploaded scene refitted on the device to new triangle coordinates --
         coords: a contiguous float32 tensor [n_triangles, 3, 3] on this device (the new triangle_t.coords, original

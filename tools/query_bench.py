@@ -19,7 +19,9 @@ rt_sweep_spheres beside the closest-hit query on the same rays (sweep_mode below
 rt_cut_triangles beside rt_overlap_boxes on the query triangles' corner boxes (cuts_mode below), --mode
 contacts rt_sweep_contacts beside rt_sweep_spheres on the same sweeps (contacts_mode below), --mode
 clearance rt_clearance_triangles beside rt_cut_triangles' count on the same triangles and rt_nearest_points on their
-centroids (clearance_mode below).
+centroids (clearance_mode below), --mode proximity rt_proximity_triangles' lists beside
+rt_clearance_triangles, its counts within a margin beside rt_cut_triangles' count, and its CSR form (proximity_mode
+below).
 usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --height 1080] [--runs 7]
        python tools/query_bench.py --mode shade [--regroups 4 16 32] [--runs 15]
        python tools/query_bench.py --mode hits [--runs 7]
@@ -29,7 +31,8 @@ usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --h
        python tools/query_bench.py --mode sweep [--runs 7] [--out profiles/sweep_bench_<md5>.jsonl]
        python tools/query_bench.py --mode cuts [--runs 5] [--out profiles/cuts_bench_<md5>.jsonl]
        python tools/query_bench.py --mode contacts [--runs 5] [--out profiles/contacts_bench_<md5>.jsonl]
-       python tools/query_bench.py --mode clearance [--runs 5] [--out profiles/clearance_bench_<md5>.jsonl]"""
+       python tools/query_bench.py --mode clearance [--runs 5] [--out profiles/clearance_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode proximity [--runs 3] [--out profiles/proximity_bench_<md5>.jsonl]"""
 import argparse
 import json
 import os
@@ -47,7 +50,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts",
-                                       "contacts", "clearance"],
+                                       "contacts", "clearance", "proximity"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
@@ -58,7 +61,9 @@ def main():
                          "cuts: rt_cut_triangles beside rt_overlap_boxes on the corner boxes (cuts_mode); "
                          "contacts: rt_sweep_contacts beside rt_sweep_spheres (contacts_mode); "
                          "clearance: rt_clearance_triangles beside rt_cut_triangles' count and rt_nearest_points "
-                         "(clearance_mode)")
+                         "(clearance_mode); "
+                         "proximity: rt_proximity_triangles beside rt_clearance_triangles and rt_cut_triangles' count "
+                         "(proximity_mode)")
     ap.add_argument("--out", default=None,
                     help="nearest, neighbours, overlap, sweep, cuts, contacts: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
@@ -86,6 +91,8 @@ def main():
         return contacts_mode(a, md5)
     if a.mode == "clearance":
         return clearance_mode(a, md5)
+    if a.mode == "proximity":
+        return proximity_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -804,26 +811,7 @@ def clearance_mode(a, md5):
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
         r.upload(s)
-        o, d, g, _ = point_sets(r, s, W, H)
-        hit, t = r.trace_rays(o, d, kernel="fast")
-        r.sync()
-        t = torch.where(hit >= 0, t, torch.ones_like(t))
-        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
-        slo, shi = v.min(0), v.max(0)
-        ext = float((shi - slo).max())
-        off = torch.randn(n, 3, 3, generator=g)
-        off = (off - off.mean(dim=1, keepdim=True)).cuda()
-        sets = []
-        for pct in (0.1, 1.0, 5.0):
-            size = ext * pct / 100
-            for lift, what in ((0.0, "on"), (3.0 * size, "lifted")):
-                ctr = (o + d * (t - lift / d.norm(dim=1))[:, None]).contiguous()
-                sets.append((f"hit_points_{pct}pct_{what}", (ctr[:, None, :] + off * size).contiguous(), size))
-        dims = (1440, 720) if n == 2073600 else (W, max(H // 2, 1))
-        su = np.array([shi[0] - slo[0], 0.0, 0.0], np.float32)
-        sv = np.array([0.0, shi[1] - slo[1], 0.0], np.float32)
-        sheet = tris.sheet(np.array([slo[0], slo[1], slo[2] - 0.05 * ext], np.float32), su, sv, dims)
-        sets.append((f"sheet_beside_{dims[0]}x{dims[1]}", sheet, float(max(su[0] / dims[0], sv[1] / dims[1]))))
+        sets, g, _ = triangle_sets(r, s, W, H)
         for label, q, size in sets:
             m = len(q)
             pick = torch.randperm(m, generator=g)[:NS].cuda()
@@ -873,6 +861,137 @@ def clearance_mode(a, md5):
                         "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
                         "tests_per_query": round(tested / cnt[k], 2),
                         "gated_per_query": round(info.get("pairs_gated", 0) / cnt[k], 2),
+                        "info": {x: w for x, w in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+        r.close()
+    if out:
+        out.close()
+
+
+def triangle_sets(r, s, W, H):
+    """clearance_mode's query sets -> ([(label, tris [m, 3, 3] on the device, size)], the generator, the scene's extent)"""
+    import numpy as np
+    import torch
+    from prt import tris
+    n = W * H
+    o, d, g, _ = point_sets(r, s, W, H)
+    hit, t = r.trace_rays(o, d, kernel="fast")
+    r.sync()
+    t = torch.where(hit >= 0, t, torch.ones_like(t))
+    v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+    slo, shi = v.min(0), v.max(0)
+    ext = float((shi - slo).max())
+    off = torch.randn(n, 3, 3, generator=g)
+    off = (off - off.mean(dim=1, keepdim=True)).cuda()
+    sets = []
+    for pct in (0.1, 1.0, 5.0):
+        size = ext * pct / 100
+        for lift, what in ((0.0, "on"), (3.0 * size, "lifted")):
+            ctr = (o + d * (t - lift / d.norm(dim=1))[:, None]).contiguous()
+            sets.append((f"hit_points_{pct}pct_{what}", (ctr[:, None, :] + off * size).contiguous(), size))
+    dims = (1440, 720) if n == 2073600 else (W, max(H // 2, 1))
+    su = np.array([shi[0] - slo[0], 0.0, 0.0], np.float32)
+    sv = np.array([0.0, shi[1] - slo[1], 0.0], np.float32)
+    sheet = tris.sheet(np.array([slo[0], slo[1], slo[2] - 0.05 * ext], np.float32), su, sv, dims)
+    sets.append((f"sheet_beside_{dims[0]}x{dims[1]}", sheet, float(max(su[0] / dims[0], sv[1] / dims[1]))))
+    return sets, g, ext
+
+
+def proximity_mode(a, md5):
+    """--mode proximity: per scene, on clearance_mode's query sets (triangle_sets), rt_proximity_triangles
+    with k = 1, 4, 8 and 16 (tri, d2, both points and kind written) beside rt_clearance_triangles on the same queries;
+    its pure count within margins of 0.1 % and 1 % of the scene's extent beside rt_cut_triangles' pure count; and
+    Renderer.proximity_csr at the 0.1 % margin (two launches and the sorts: wall time around the call, after a
+    synchronise, not kernel_ms; skipped with its reason where the total does not fit). One untimed round first; then
+    --runs rounds with the arms interleaved; kernel_ms from the HIP events around each launch. One JSON line per arm:
+    median / min / max ms, the ratio of the median to clearance's, nodes_visited, pairs_tested and pairs_gated per
+    query, stored and counted per query, the counters, and whether the fast kernel's list of 8 and count equal the
+    exhaustive kernel's on 4,096 of the queries (every output's bits)."""
+    import time
+
+    import torch
+    from prt import device, host
+    W, H = a.width, a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        sets, g, ext = triangle_sets(r, s, W, H)
+        for label, q, size in sets:
+            m = len(q)
+            pick = torch.randperm(m, generator=g)[:NS].cuda()
+            qs = q[pick].contiguous()
+            margins = {pct: torch.full((m,), (ext * pct / 100) ** 2, dtype=torch.float32, device="cuda")
+                       for pct in (0.1, 1.0)}
+            kinds = {k: torch.empty((m, k), dtype=torch.int32, device="cuda") for k in (1, 4, 8, 16)}
+            ckind = torch.empty(m, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+
+            def clearance():
+                r.clearance(q, kind=ckind)
+                return r.clearance_info()
+
+            def lists(k):
+                r.proximity(q, k=k, pairs_out=True, kind=kinds[k])
+                return r.proximity_info()
+
+            def count(pct):
+                r.proximity(q, k=0, count_all=True, max_dist2=margins[pct])
+                return r.proximity_info()
+
+            def cut_count():
+                r.cuts(q, k=0, count_all=True)
+                return r.cuts_info()
+
+            def csr():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                try:
+                    off = r.proximity_csr(q, margins[0.1])[0]
+                except device.RtError as e:
+                    return {"kernel_ms": float("nan"), "skipped": str(e)}
+                torch.cuda.synchronize()
+                info = r.proximity_info()
+                info["kernel_ms"] = (time.perf_counter() - t0) * 1e3  # (wall time of the whole call)
+                info["total"] = int(off[-1])
+                return info
+
+            def sample(k, **kw):
+                x = [r.proximity(qs, k=k, pairs_out=k > 0, kernel=kern, **kw) for kern in ("fast", "strict")]
+                r.sync()
+                return all(bool((p.view(torch.int32) == w.view(torch.int32)).all()) for p, w in zip(*x))
+
+            same = sample(8) and sample(0, count_all=True, max_dist2=margins[1.0][:NS].contiguous())
+            arms = [("clearance", clearance)] + [(f"proximity_k{k}", lambda k=k: lists(k)) for k in (1, 4, 8, 16)] + \
+                   [(f"count_{pct}pct", lambda pct=pct: count(pct)) for pct in (0.1, 1.0)] + \
+                   [("cut_count", cut_count), ("csr_0.1pct", csr)]
+            for _, fn in arms:  # the untimed round
+                fn()
+            ms, last = {k: [] for k, _ in arms}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                line = {"scene": name, "set": label, "arm": k, "queries": m, "size": round(size, 6),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_clearance": round(med[k] / med["clearance"], 3),
+                        "ratio_to_cut_count": round(med[k] / med["cut_count"], 3), "runs": a.runs,
+                        "wall_time": k.startswith("csr"),
+                        "sample_equals_exhaustive": same if k in ("proximity_k8", "count_1.0pct") else None,
+                        "nodes_visited_per_query": round(info.get("nodes_visited", 0) / m, 2),
+                        "tests_per_query": round(info.get("pairs_tested", 0) / m, 2),
+                        "gated_per_query": round(info.get("pairs_gated", 0) / m, 2),
+                        "stored_per_query": round(info.get("stored", 0) / m, 2),
+                        "counted_per_query": round(info.get("counted", 0) / m, 2),
                         "info": {x: w for x, w in info.items() if x != "kernel_ms"}, "lib_md5": md5}
                 print(json.dumps(line), flush=True)
                 if out:
