@@ -238,7 +238,15 @@ int rt_device_count(void);
 const char* rt_version(void);
 
 int rt_create(const rt_opts* opts, rt_ctx** out);
-/* load_to_gpu(): converts the reference layouts into the device layout and uploads */
+/* The largest |coordinate| of a scene, at an upload and at every update: 2^123 (1.06e37). A wide view's planes lie on a
+ * per-node grid whose origin is 1,024 steps below the node's boxes (rt_quant.hpp); up to here that origin, the step
+ * 2^e (e <= 117) and every decoded plane are finite floats, beyond it they need not be. rt_upload_scene and
+ * rt_update_vertices (rt_rebuild_views with it) answer RT_E_ARG for a larger coordinate and change nothing; the host
+ * builders (rth_wbvh_build, rth_wbvh_build_greedy, rth_wbvh_refit) answer RT_E_ARG where a grid does not fit. */
+#define RT_COORD_MAX 0x1p123f
+/* load_to_gpu(): converts the reference layouts into the device layout and uploads. Where the fast view's
+ * collapse fails or its product does not pass rth_wbvh_check, the scene has no wide view (rt_scene_info.wide_nodes = 0)
+ * and the fast kernels answer from the other trees or the exhaustive loops: never from a view that misses triangles. */
 int rt_upload_scene(rt_ctx* ctx, const rt_scene* scene);
 int rt_get_scene_info(rt_ctx* ctx, rt_scene_info* info);
 /* render_frame(): enqueues ONE kernel on the context stream (asynchronous) */
@@ -1028,8 +1036,8 @@ int rt_get_proximity_info(rt_ctx* ctx, rt_proximity_info* info);
  * The default rule's per-shape launch decisions survive an update (an animation does not re-trial every frame); the
  * query and shade state is untouched; the inflation 2^-16 x magnitude and the queries' origin bound follow the new
  * coordinates.
- * Errors: RT_E_STATE before an upload; RT_E_ARG for a null pointer, a count mismatch or a non-finite coordinate --
- * found by a read-only first pass, so a refused update leaves the scene exactly as it was.
+ * Errors: RT_E_STATE before an upload; RT_E_ARG for a null pointer, a count mismatch, a non-finite coordinate or one
+ * beyond RT_COORD_MAX -- found by a read-only first pass, so a refused update leaves the scene exactly as it was.
  * coords is read in stream order on the context stream. The call waits on the host once, for that first pass's few
  * words (and, the first time after an upload or a rebuild, before that pass, for the trees' level lists and the face
  * lists' buffers); everything after is asynchronous, except a view's rebuild. */

@@ -45,7 +45,8 @@ int rth_triangles_random(size_t n, rth_rng* g, rt_triangle** out);
  * heuristic: 0 axis-0 centre, 1 largest-axis centre, 3 random axis/position (cpu default,
  *   options.h:34; consumes g), 6 32-bin SAH with the reference's FLT_MIN box seed (gpu default,
  *   options.cuh:50), RTH_BVH_BINNED_SAH: this library's O(n log n) binned SAH (surface-area cost,
- *   leaf <= 8, depth <= 24) for large meshes. Leaves: tr_len <= 2 or depth 32 (bvh.c:84). Output uses the
+ *   leaf <= 8, depth <= 24) for large meshes (RT_E_ARG for a centroid that is not finite: its bins are
+ *   formed from them). Leaves: tr_len <= 2 or depth 32 (bvh.c:84). Output uses the
  *   reference's node layout; nodes has bvh_len entries. */
 enum { RTH_BVH_BINNED_SAH = 16 };
 typedef struct rth_bvh_stats {
@@ -71,7 +72,10 @@ int rth_bvh_build_cached(const rt_triangle* tris, size_t n, int heuristic, rth_r
  * hold up to 8 children; child boxes are grown by `inflate` and quantised outward to 8 bits per
  * plane; leaves hold <= 4 triangles. Replaces no reference function: it is the acceleration structure
  * behind RT_ACCEL_AUTO. nodes: 20 x uint32 per node, root = node 0; tri_order: wide-leaf position
- * -> triangle index (a permutation of 0..n_tris-1). Buffers are released with rth_free(). */
+ * -> triangle index (a permutation of 0..n_tris-1). Buffers are released with rth_free().
+ * The collapse's costs are formed on lengths divided by the power of two above the root's longest side, so a scene
+ * of any finite size gets the view of its copy of unit size. RT_E_ARG (from the refit too, whose nodes are then
+ * partly rewritten) where no grid of finite planes holds a node's boxes: coordinates beyond RT_COORD_MAX, rt_hip.h. */
 typedef struct rth_wbvh_info {
     int n_nodes, n_tris, depth, max_children;
 } rth_wbvh_info;

@@ -828,15 +828,19 @@ float scene_magnitude(const rt_triangle* T, int n) {
 }
 
 // A binary tree in the reference layout collapsed to the 8-wide quantised form (rt_wide.cpp; boxes inflated, planes
-// rounded outward) over its n triangles; false: none (the collapse failed, or too deep for the wide walk's stack).
+// rounded outward) over its n triangles; false: none (the collapse failed, its product does not pass rth_wbvh_check --
+// every triangle in exactly one leaf slot of 1..4, every node but the root with one parent -- or has fewer nodes than
+// n triangles need at 32 a node, or is too deep for the wide walk's stack). The check is one pass over the words.
 bool collapse_wide(rt_ctx* ctx, const rt_bvh_node* nodes, int nlen, const int* idx, const rt_triangle* T, int n,
                    float inflate, float cnode, HostWide& w) {
     uint32_t* words = nullptr;
     int* order = nullptr;
     rth_wbvh_info wi{};
     const auto t_c = std::chrono::steady_clock::now();
-    const bool built = rth_wbvh_build_cost(nodes, nlen, idx, T, n, inflate, cnode, &words, &order, &wi) == RT_OK;
+    bool built = rth_wbvh_build_cost(nodes, nlen, idx, T, n, inflate, cnode, &words, &order, &wi) == RT_OK;
     ctx->t_collapse += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_c).count();
+    built = built && wi.n_tris == n && (long long)wi.n_nodes * 32 >= n &&
+            rth_wbvh_check(words, wi.n_nodes, order, n, 0, nullptr) == RT_OK;
     const bool ok = built && wi.depth <= rtd::WSTACK;
     if (ok) {
         w.nodes.resize(5 * (size_t)wi.n_nodes);
@@ -915,6 +919,7 @@ extern "C" int rt_upload_scene(rt_ctx* ctx, const rt_scene* sc) {
     HostWide wide, unit, prim;
     // the boxes' inflation: 2^-16 of the scene's coordinate magnitude (>= 20x the slab tests' rounding reach)
     const float scene_mx = scene_magnitude(sc->triangles, n);
+    if (!(scene_mx <= RT_COORD_MAX)) return arg_err(ctx, "rt_upload_scene: a coordinate is beyond RT_COORD_MAX");
     const float inflate = std::ldexp(scene_mx, -16);
     int rc = build_view(ctx, sc->bvh, sc->n_nodes, sc->tri_idx, sc->triangles, n, 0.0f, hr);
     if (rc) return rc;
@@ -2546,6 +2551,8 @@ int update_vertices(rt_ctx* ctx, const rt_vertex_update* u, bool report, float* 
     if (ctx->h_plan[rtr::P_BAD]) return arg_err(ctx, "rt_update_vertices: a coordinate is not finite (nothing was changed)");
     float scene_mx;
     std::memcpy(&scene_mx, &ctx->h_plan[rtr::P_MX], 4);
+    if (!(scene_mx <= RT_COORD_MAX))
+        return arg_err(ctx, "rt_update_vertices: a coordinate is beyond RT_COORD_MAX (nothing was changed)");
     const float inflate = std::ldexp(scene_mx, -16);
     rt_update_info ui{};
     ui.joined_unit = (int)ctx->h_plan[rtr::P_JOIN_UNIT];

@@ -22,6 +22,8 @@ namespace rtq {
 
 constexpr int QBIAS = 1024;  // rt_wide.cpp QBIAS
 constexpr int WIDTH = 8;
+constexpr int E_MAX = 117;   // the largest grid exponent: QBIAS * 2^E_MAX = 2^127 is still a float
+constexpr int E_NONE = 127;  // quantise_axis: no grid holds the boxes
 
 RTQ_HD float u2f(uint32_t u) {
     float f;
@@ -60,7 +62,10 @@ RTQ_HD int start_exponent(double ext) {
 RTQ_HD int steps(double q) { return (int)(q < -1e9 ? -1e9 : (q > 1e9 ? 1e9 : q)); }
 
 // Quantise one axis of k <= 8 child boxes (already grown) on the grid pb + 2^e * (QBIAS + q), q in 0..255. Returns the
-// grid's exponent e (-126 .. 110); pb receives the grid's origin, qlo / qhi the planes.
+// grid's exponent e (-126 .. E_MAX); pb receives the grid's origin, qlo / qhi the planes. E_NONE: no exponent up to
+// E_MAX gives a grid with a finite origin whose decoded planes contain the boxes; pb and the planes are then not
+// valid. With max|coordinate| <= RT_COORD_MAX = 2^123 (include/rt_hip.h) that cannot happen: the grown boxes span at
+// most 2^124 (1 + 2^-16), about half of the 255 * 2^117 that E_MAX spans, and the origin lies within 2^123 + 2^127 of 0.
 RTQ_HD int quantise_axis(const float* lo, const float* hi, int k, float& pb, int* qlo, int* qhi) {
     float p = lo[0], top = hi[0];
     for (int c = 1; c < k; c++) {
@@ -69,8 +74,8 @@ RTQ_HD int quantise_axis(const float* lo, const float* hi, int k, float& pb, int
     }
     const double ext = (double)top - (double)p;
     int e = ext > 0 ? start_exponent(ext) : -126;
-    e = e < -126 ? -126 : (e > 100 ? 100 : e);  // (QBIAS * 2^e stays finite)
-    for (;; e++) {
+    e = e < -126 ? -126 : (e > 100 ? 100 : e);
+    for (; e <= E_MAX; e++) {  // (QBIAS * 2^e stays finite)
         const float scale = pow2(e);
         pb = round_down((double)p - (double)QBIAS * scale);  // q = 0 decodes to the lowest plane or below it
         // (a lowest plane more than 2^52 times smaller than QBIAS * 2^e vanishes from that double difference: step down
@@ -88,8 +93,9 @@ RTQ_HD int quantise_axis(const float* lo, const float* hi, int k, float& pb, int
             qlo[c] = a;
             qhi[c] = b;
         }
-        if (ok || e >= 110) return e;
+        if (ok) return e;
     }
+    return E_NONE;
 }
 
 // ---- a wide node's 20 words (rt_device.hpp DWide), topology fields
@@ -145,8 +151,9 @@ RTQ_HD double decoded_area(const uint32_t* W) {
 // Re-quantise a node in place from its occupied slots' exact child boxes (box[s], read for occupied slots only), each
 // grown by `inflate`: rewrites the origin p, the three exponents and the plane words; imask, child_base, tri_base, meta
 // and the slot assignment stay. The collapse's own arithmetic (rt_wide.cpp form): slots in rising order, lo - inflate
-// and hi + inflate in float, empty slots an inverted box (255, 0).
-RTQ_HD void requantise(uint32_t* W, const Box* box, float inflate) {
+// and hi + inflate in float, empty slots an inverted box (255, 0). false: an axis has no grid (quantise_axis' E_NONE);
+// the node is left as it was.
+RTQ_HD bool requantise(uint32_t* W, const Box* box, float inflate) {
     float lo[3][WIDTH], hi[3][WIDTH];
     int qlo[3][WIDTH], qhi[3][WIDTH];
     int slot_list[WIDTH];
@@ -159,10 +166,11 @@ RTQ_HD void requantise(uint32_t* W, const Box* box, float inflate) {
             }
             slot_list[ks++] = s;
         }
-    if (ks == 0) return;
+    if (ks == 0) return true;
     float p[3];
     int eb[3];
     for (int a = 0; a < 3; a++) eb[a] = quantise_axis(lo[a], hi[a], ks, p[a], qlo[a], qhi[a]);
+    if (eb[0] == E_NONE || eb[1] == E_NONE || eb[2] == E_NONE) return false;
     W[0] = f2u(p[0]);
     W[1] = f2u(p[1]);
     W[2] = f2u(p[2]);
@@ -181,6 +189,7 @@ RTQ_HD void requantise(uint32_t* W, const Box* box, float inflate) {
     }
     for (int a = 0; a < 3; a++)
         for (int j = 0; j < WIDTH / 2; j++) W[8 + 4 * a + j] = planes[a][j];
+    return true;
 }
 
 }  // namespace rtq

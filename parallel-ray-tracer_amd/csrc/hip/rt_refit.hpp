@@ -203,7 +203,7 @@ __global__ __launch_bounds__(64) void k_wide_level(int first, int count, float4*
         }
         exact[2 * (size_t)k] = make_float4(own.lo[0], own.lo[1], own.lo[2], 0.0f);
         exact[2 * (size_t)k + 1] = make_float4(own.hi[0], own.hi[1], own.hi[2], 0.0f);
-        rtq::requantise(W, box, inflate);
+        (void)rtq::requantise(W, box, inflate);  // (never false: rt_update_vertices refuses coordinates beyond RT_COORD_MAX)
         // (the topology words are written back as read)
         for (int j = 0; j < 5; j++)
             nodes[5 * (size_t)k + j] = make_float4(__int_as_float((int)W[4 * j]), __int_as_float((int)W[4 * j + 1]),

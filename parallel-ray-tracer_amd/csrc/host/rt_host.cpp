@@ -363,6 +363,11 @@ struct Builder {
         mx.z = std::max(mx.z, b[5]);
     }
 
+    // a centroid's bin. x = (centroid - lowest) * bins / extent lies in [0, bins]; where the extent is no float (+inf,
+    // the scale 0) it is 0 or, for an offset that is +inf too, NaN, whose conversion to int is undefined (it indexed
+    // the bins at INT_MIN): bin 0 then
+    static int bin_of(float x, int nb) { return x >= 0.0f ? (x < (float)nb ? (int)x : nb - 1) : 0; }
+
     void sah_split(int ni, int depth) {
         rt_bvh_node* p = &bvh[ni];
         const int first = p->child, cnt = p->tr_len;
@@ -395,7 +400,7 @@ struct Builder {
             const float sc = NB / ext;
             for (int i = first; i < first + cnt; i++) {
                 int t = idx[i];
-                int b = std::min(NB - 1, (int)((cen[3 * t + a] - cmn[a]) * sc));
+                int b = bin_of((cen[3 * t + a] - cmn[a]) * sc, NB);
                 bc[b]++;
                 grow_sah(bmn[b], bmx[b], t);
             }
@@ -444,7 +449,7 @@ struct Builder {
             const float ext = cmx[a] - cmn[a], sc = NB / ext, lo = cmn[a];
             int* beg = idx.data() + first;
             int* m = std::partition(beg, beg + cnt, [&](int t) {
-                return std::min(NB - 1, (int)((cen[3 * t + a] - lo) * sc)) <= best_bin;
+                return bin_of((cen[3 * t + a] - lo) * sc, NB) <= best_bin;
             });
             mid = (int)(m - idx.data());
             if (mid == first || mid == first + cnt) mid = first + cnt / 2;
@@ -482,6 +487,10 @@ extern "C" int rth_bvh_build(const rt_triangle* tris, size_t n, int heuristic, r
     if (heuristic != 0 && heuristic != 1 && heuristic != 3 && heuristic != 6 && heuristic != RTH_BVH_BINNED_SAH)
         return RT_E_ARG;
     if (heuristic == 3 && !g) return RT_E_ARG;
+    if (heuristic == RTH_BVH_BINNED_SAH)  // (its bins are formed from the centroids)
+        for (size_t i = 0; i < n; i++)
+            for (int a = 0; a < 3; a++)
+                if (!std::isfinite(tris[i].centroid[a])) return RT_E_ARG;
     Builder b;
     b.tris = tris;
     b.n = (int)n;

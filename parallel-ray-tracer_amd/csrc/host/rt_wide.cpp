@@ -52,8 +52,10 @@ void grow(Box& b, const Box& o) {
     }
 }
 
-float area(const Box& b) {
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
+// the area of a box whose sides are scaled by 2^-s (exactly, but for a side that becomes a denormal)
+float area(const Box& b, int s) {
+    const float dx = std::ldexp(b.hi[0] - b.lo[0], -s), dy = std::ldexp(b.hi[1] - b.lo[1], -s),
+                dz = std::ldexp(b.hi[2] - b.lo[2], -s);
     return 2.0f * (dx * dy + dy * dz + dz * dx);
 }
 
@@ -135,20 +137,30 @@ struct WBuilder {
     // ---- SAH-optimal collapse (Ylitie et al. 2017, §3.1): cost(n, i) = cheapest way to hang subtree n
     // off a parent using at most i slots — as one leaf slot (<= LEAF_MAX triangles), as one wide node,
     // or by distributing the slots over n's two children. Costs are surface area x (C_node per wide-node
-    // visit, 1 per triangle test).
+    // visit, 1 per triangle test), on lengths divided by 2^area_exp, the power of two above the root's longest side: the
+    // costs of a scene are those of the same scene scaled by any power of two, and stay finite and nonzero where a
+    // box's own area (1e40 for sides of 1e20, 1e-46 for sides of 1e-23) is no float. Were they all +inf or all 0,
+    // every comparison below would tie and the root would come out as one "leaf" of the whole scene.
+    int area_exp = 0;
     struct Dp {  // one node's costs, side by side (the collapse reads them node by node, in no memory order)
         float cost[WIDTH + 1];
         signed char split[WIDTH + 1];  // dist(n, i): slots given to the left child
         char as_leaf;                  // cost(n, 1) is the leaf form
     };
     std::unique_ptr<Dp[]> dp;  // (uninitialised: every node's entry is written before it is read)
-    void sah_begin() { dp.reset(new Dp[bn.size()]); }
+    void sah_begin(int root) {
+        dp.reset(new Dp[bn.size()]);
+        const Box& b = bn[root].b;
+        const float side = std::max(b.hi[0] - b.lo[0], std::max(b.hi[1] - b.lo[1], b.hi[2] - b.lo[2]));
+        area_exp = 0;
+        if (side > 0.0f && std::isfinite(side)) (void)std::frexp(side, &area_exp);
+    }
     // nodes [n0, n1) of bn, whose children precede them within the range or in ranges already costed
     void sah_costs(size_t n0, size_t n1, float c_node) {
         for (size_t n = n0; n < n1; n++) {  // children precede parents in bn
             const BNode& B = bn[n];
             Dp& D = dp[n];
-            const float A = area(B.b);
+            const float A = area(B.b, area_exp);
             const float leaf = (B.cnt > 0 && B.cnt <= LEAF_MAX) ? A * (float)B.cnt : INFINITY;
             if (B.l < 0) {
                 for (int i = 1; i <= WIDTH; i++) D.cost[i] = leaf;
@@ -238,7 +250,9 @@ inline uint32_t f2u(float f) {
 }
 
 // Quantise one axis of up to 8 child boxes (already grown) on the grid pb + 2^e * (QBIAS + q), q in 0..255.
-// Returns the grid's exponent e (-126 .. 110); pb receives the grid's origin, qlo/qhi the planes.
+// Returns the grid's exponent e (-126 .. rtq::E_MAX); pb receives the grid's origin, qlo/qhi the planes. rtq::E_NONE:
+// no grid of a finite origin holds the boxes (coordinates beyond RT_COORD_MAX, include/rt_hip.h); the planes are then
+// not valid.
 int quantise_axis(const float* lo, const float* hi, int k, float& pb, int* qlo, int* qhi) {
     float p = INFINITY, top = -INFINITY;
     for (int c = 0; c < k; c++) {
@@ -247,24 +261,29 @@ int quantise_axis(const float* lo, const float* hi, int k, float& pb, int* qlo, 
     }
     const double ext = (double)top - (double)p;
     int e = ext > 0 ? (int)std::ceil(std::log2(ext / 255.0)) : -126;
-    e = std::max(-126, std::min(e, 100));  // (QBIAS * 2^e stays finite)
-    for (;; e++) {
+    e = std::max(-126, std::min(e, 100));
+    for (; e <= rtq::E_MAX; e++) {  // (QBIAS * 2^e stays finite)
         const float scale = std::ldexp(1.0f, e);
         pb = round_down((double)p - (double)QBIAS * scale);  // q = 0 decodes to the lowest plane or below it
+        // (a lowest plane more than 2^52 times smaller than QBIAS * 2^e -- -1.8e-16 beside a box 0.7 wide, without an
+        // inflation -- vanishes from that double difference, and q = 0 decoded to 0, above it, at every exponent: step
+        // down as rt_quant.hpp does; never taken while the difference is exact)
+        for (int i = 0; i < 4 && fma_decode(scale, 0, pb) > p; i++) pb = std::nextafter(pb, -INFINITY);
         bool ok = true;
         for (int c = 0; c < k && ok; c++) {
-            int a = (int)std::floor(((double)lo[c] - (double)pb) / scale) - QBIAS;
+            int a = rtq::steps(std::floor(((double)lo[c] - (double)pb) / scale)) - QBIAS;
             a = std::max(0, std::min(a, 255));
             while (a > 0 && fma_decode(scale, a, pb) > lo[c]) a--;
-            int b = (int)std::ceil(((double)hi[c] - (double)pb) / scale) - QBIAS;
+            int b = rtq::steps(std::ceil(((double)hi[c] - (double)pb) / scale)) - QBIAS;
             b = std::max(0, b);
             while (b <= 255 && fma_decode(scale, b, pb) < hi[c]) b++;
             if (b > 255 || fma_decode(scale, a, pb) > lo[c]) ok = false;
             qlo[c] = a;
             qhi[c] = b;
         }
-        if (ok || e >= 110) return e;
+        if (ok) return e;
     }
+    return rtq::E_NONE;
 }
 
 }  // namespace
@@ -370,7 +389,7 @@ extern "C" int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const in
     // measured sweep — dragon -3.5 % vs 4, car_boxed even; the greedy largest-area collapse: +1.6 % / +3 %;
     // DESIGN.md §3). The subtrees' ranges of bn on the threads, then the top.
     const float cn = c_node > 0.0f ? c_node : 2.0f;
-    w.sah_begin();
+    w.sah_begin(root);
     if (front.size() > 1)
         run_tasks(front.size(), [&](size_t k) { w.sah_costs(pbase[k], pbase[k + 1], cn); });
     w.sah_costs(pbase[front.size()], w.bn.size(), cn);
@@ -387,6 +406,7 @@ extern "C" int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const in
         char leaf[WIDTH];    // per slot: a leaf slot
         int n_inner, n_tri;  // interior slots, leaf triangles
     };
+    std::atomic<bool> unfit{false};  // a node whose planes hold no grid, or a leaf slot of no or too many triangles
     auto form = [&](const Item& it, Out& o) {
         const BNode& B = w.bn[it.b];
         std::pair<int, bool> c2[WIDTH];
@@ -447,7 +467,12 @@ extern "C" int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const in
             }
         float p[3];
         int eb[3];
-        for (int a = 0; a < 3; a++) eb[a] = quantise_axis(lo[a], hi[a], ks, p[a], qlo[a], qhi[a]);
+        for (int a = 0; a < 3; a++) {
+            eb[a] = quantise_axis(lo[a], hi[a], ks, p[a], qlo[a], qhi[a]);
+            if (eb[a] == rtq::E_NONE) unfit = true;
+        }
+        for (int c = 0; c < k; c++)  // (a leaf slot is 1..4 triangles, whatever the costs said)
+            if (c2[c].second && (w.bn[c2[c].first].cnt < 1 || w.bn[c2[c].first].cnt > LEAF_MAX)) unfit = true;
         uint32_t* W = o.W;
         std::memset(W, 0, sizeof o.W);
         W[0] = f2u(p[0]);
@@ -508,6 +533,7 @@ extern "C" int rth_wbvh_build_cost(const rt_bvh_node* bvh, int n_nodes, const in
         depth = std::max(depth, level[0].depth);
         outs.resize(level.size());
         parallel(level.size(), [&](size_t i) { form(level[i], outs[i]); });
+        if (unfit) return RT_E_ARG;  // (coordinates beyond RT_COORD_MAX; a leaf the binary tree cannot be cut to)
         // bases in queue order: this level's children follow every node queued so far
         size_t next_node = n_wide + level.size(), next_tri = n_order;
         std::vector<size_t> cbase(level.size()), tbase(level.size());
@@ -601,7 +627,7 @@ extern "C" int rth_wbvh_refit(uint32_t* nodes, int n_nodes, const int* tri_order
             rtq::grow(own, box[s]);
         }
         exact[k] = own;
-        rtq::requantise(W, box, inflate);
+        if (!rtq::requantise(W, box, inflate)) return RT_E_ARG;  // (coordinates beyond RT_COORD_MAX)
     }
     return RT_OK;
 }
