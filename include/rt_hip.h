@@ -1015,6 +1015,105 @@ typedef struct rt_proximity_info {
  * not valid), RT_E_STATE before the first */
 int rt_get_proximity_info(rt_ctx* ctx, rt_proximity_info* info);
 
+/* Triangle sweep queries: per caller-supplied moving triangle the first contact with the mesh -- rt_clearance_triangles'
+ * motion form, as rt_sweep_spheres is a point query's (continuous collision of a part, a tool or a cloth face against the
+ * mesh, how far a placed component can travel along a direction before it clashes, the time of impact a contact solver
+ * needs so that a face does not tunnel through a thin sheet between two samples).
+ * Query i is a triangle q0, q1, q2 that translates without rotating: its corners at time t are q + t d, d not
+ * normalised, over 0 <= t <= T with T = fminf(t_max[i], FLT_MAX) (t_max NULL or +inf: no bound). Its answer is the first
+ * element of
+ *   S_i = { j : toi(i, triangle j) exists and <= T }, ordered by (toi ascending, original index ascending):
+ * a total order, so the answer depends on no BVH, and an exact tie (triangles that share the touched edge or corner)
+ * goes to the lower index. S_i is empty, decided before any walk, when one of the twelve numbers of q0, q1, q2, d is
+ * non-finite, and when t_max[i] is NaN or negative (the sign read from the bits: a negative subnormal is negative, -0 is
+ * the bound 0). t_max = 0 and d = 0 both ask "does it touch now". No input value is an error.
+ * Every operation is one float32 operation and nothing is contracted into an FMA. dot(u, v) = u.x*v.x + u.y*v.y + u.z*v.z
+ * left to right; cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x); fminf / fmaxf with C semantics
+ * (a NaN operand loses); IEEE division; a comparison with a NaN operand is false.
+ *   1. Records and boxes are rt_clearance_triangles' own. The mesh triangle is its record a = v0, e1 = fl(v1 - v0),
+ *      e2 = fl(v2 - v0) with corners a, b = fl(a + e1), c = fl(a + e2) and corner box [tlo, thi]. The query is made a
+ *      record the same way: f1 = fl(q1 - q0), f2 = fl(q2 - q0), qb = fl(q0 + f1), qc = fl(q0 + f2); [qlo, qhi] is the
+ *      componentwise fminf / fmaxf over the FIVE points q0, q1, q2, qb, qc (folded in that order).
+ *   2. The gate. t0 = 0; t1 = T; then for each axis k:
+ *        d.k == 0: the triangle is out unless qlo.k <= thi.k && tlo.k <= qhi.k
+ *        else      inv = 1 / d.k; ta = (tlo.k - qhi.k) * inv; tb = (thi.k - qlo.k) * inv
+ *                  t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb))
+ *      the triangle is out unless t0 <= t1. (rt_sweep_spheres' slab gate with the query's box in the sphere's place.)
+ *   3. Recentre. sh = d*t0; r0 = q0 + sh, r1 = q1 + sh, r2 = q2 + sh, rb = qb + sh, rc = qc + sh. f1 and f2 keep their
+ *      bits.
+ *   4. A start in contact. If rt_cut_triangles' X(r0, r1, r2; triangle) holds -- that test unchanged, on the recentred
+ *      raw corners --, then toi = t0, kind = 15 and the point is the cut segment's first end s0. (With t0 > 0 this is a
+ *      query whose box and the triangle's first meet where the triangles do, as on an axis-aligned wall.)
+ *   5. Otherwise fifteen candidates u >= 0 measured from t0, offered in rt_clearance_triangles' order; a candidate
+ *      replaces the best only when it is valid and strictly smaller.
+ *      ray(o, dr; p, g1, g2), the one ray-triangle function, with no EPSILON culls:
+ *                h = cross(dr, g2); det = dot(g1, h); inv = 1 / det; s = o - p; bu = dot(s, h) * inv
+ *                qv = cross(s, g1); bv = dot(dr, qv) * inv; u = dot(g2, qv) * inv
+ *                valid when det != 0 && bu >= 0 && bv >= 0 && bu + bv <= 1 && u >= 0
+ *      0..2      o = r0, rb, rc: ray(o, d; a, e1, e2); the point is o + d*u
+ *      3..5      v = a, b, c: ray(v, -d; r0, f1, f2); the point is v
+ *      6..14     candidate 6 + 3*i + j is query edge i of (r0, f1), (r0, f2), (rb, fl(f2 - f1)) against mesh edge j of
+ *                (a, e1), (a, e2), (b, fl(e2 - e1)). An edge pair (p, f), (m, e):
+ *                n = cross(f, e); nn = dot(n, n); dn = dot(d, n); w0 = m - p; u = dot(w0, n) / dn
+ *                rn = 1 / nn; w = w0 - d*u; s = dot(cross(w, e), n) * rn; t = dot(cross(w, f), n) * rn
+ *                valid when nn > 0 && dn != 0 && u >= 0 && 0 <= s && s <= 1 && 0 <= t && t <= 1; the point is m + e*t
+ *      No valid candidate: the triangle is out. Otherwise toi = t0 + u (so toi >= t0 by construction), and the triangle
+ *      is in S_i iff toi <= T.
+ *   6. Results: tri[i] = the original triangle index, t[i] = toi, point[i] = the contact point on the mesh triangle
+ *      stated above, each component clamped fminf(fmaxf(., tlo), thi), kind[i] = 0..14 for the winning candidate and 15
+ *      for a start in contact. The empty set gives -1, FLT_MAX, q0's own bits and -1.
+ * The gate is monotone in the mesh-side box planes, so the walk drops a subtree whose gate interval is empty or starts
+ * strictly after the best toi so far, with no margin.
+ * Documented, not fixed:
+ *   - Motion inside the common plane of a coplanar pair gives no contact (X excludes the pair, every det and dn is 0 up
+ *     to rounding), and contacts of exactly parallel edges give none (nn = 0): a face that lands flat on a coplanar
+ *     face is reported through its corners, when they lie within the other's closed bounds.
+ *   - A query of zero area (a segment, a point) is valid and is answered by the candidates alone: X excludes it, as
+ *     rt_cut_triangles does.
+ *   - toi at a grazing contact, as with rt_sweep_spheres at r = 0, is exact only to rounding: the set differs from the
+ *     real-number one only within rounding of a contact at a boundary.
+ *   - Coordinates whose triple products overflow float32 (beyond about 2^42) make every det, dn and plane distance
+ *     infinite or NaN: no candidate is valid and the answer is the empty set.
+ * RT_KERNEL_STRICT runs every query against every triangle (the checker); RT_KERNEL_FAST walks the full 8-wide view,
+ * slots in order of their gate t0 and pruned by the best toi, and answers with the same bits. A scene without a wide view
+ * (RT_ACCEL_REFERENCE) runs the exhaustive loop under either kernel, and so does, under RT_KERNEL_FAST, a query outside
+ * the walk's domain: every |q.k| <= 2^20 mx (mx: rt_update_info.scene_magnitude's quantity) and every nonzero |d.k|
+ * within [2^-64, 2^64], where the gate makes no NaN.
+ * A triangle sweep query touches nothing a render or any other query owns. */
+typedef struct rt_sweep_tris {
+    const float* tris;   /* device, [n][3][3] f32: q0, q1, q2 of every query */
+    const float* motion; /* device, [n][3] f32: d, not normalised; a corner at time t is q + t d */
+    const float* t_max;  /* device, [n] f32, nullable (NULL or +inf: no bound) */
+    int n;               /* >= 0; 0 is RT_OK and launches nothing */
+    int kernel;          /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_sweep_tris;
+typedef struct rt_trisweep_results { /* device pointers, all nullable, at least one non-null when n > 0 */
+    int* tri;     /* [n] */
+    float* t;     /* [n] */
+    float* point; /* [n][3] */
+    int* kind;    /* [n] */
+} rt_trisweep_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null tris or motion with n > 0, all four outputs NULL with n > 0, an unknown kernel, a
+ * negative n. */
+int rt_sweep_triangles(rt_ctx* ctx, const rt_sweep_tris* tris, const rt_trisweep_results* out);
+typedef struct rt_trisweep_info {
+    long long triangles, found; /* found: query triangles with a non-empty S_i */
+    long long empty;            /* triangles - found */
+    long long walked;           /* query triangles that walked the wide view */
+    long long exhaustive;       /* query triangles run against every triangle: all valid ones under RT_KERNEL_STRICT or
+                                   without a wide view, and those outside the walk's domain (an invalid one is in neither) */
+    long long nodes_visited;    /* wide nodes decoded, summed over the queries (a level popped again counts again) */
+    long long pairs_gated;      /* the walk: triangles of a visited leaf slot turned away by their own gate (0 in the
+                                   exhaustive loop) */
+    long long pairs_tested;     /* the walk: triangles past their own gate; exhaustive: queries x triangles */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_trisweep_info;
+/* counters of the last triangle sweep query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its results
+ * are not valid), RT_E_STATE before the first */
+int rt_get_trisweep_info(rt_ctx* ctx, rt_trisweep_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

@@ -45,6 +45,7 @@
 #include "rt_cut.hpp"
 #include "rt_clearance.hpp"
 #include "rt_proximity.hpp"
+#include "rt_trisweep.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -231,7 +232,7 @@ struct rt_ctx {
     float4* h_lights = nullptr;  // pinned staging of rt_update_lights, 2 x n_lights (freed with the scene)
     hipEvent_t lights_ev = nullptr;
     float scene_mx = 16.0f;  // the scene's coordinate magnitude, as the boxes' inflation uses it (rt_upload_scene)
-    // the queries (rt_trace_rays ... rt_proximity_triangles): one slot per family (rtq::Fam), so that a query touches
+    // the queries (rt_trace_rays ... rt_sweep_triangles): one slot per family (rtq::Fam), so that a query touches
     // neither a render's state nor another family's info. counters: the family's [NCOUNT] counters, then its chunk
     // counter (made by the family's first query); ev0, ev1: around its last launch; run: a query was accepted (its info
     // can be read); launched: that query had n > 0, so the events were recorded
@@ -239,7 +240,7 @@ struct rt_ctx {
         unsigned long long* counters = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool run = false, launched = false;
-    } slots[rtq::NFAM_ALL];
+    } slots[rtq::NFAM_SLOTS];
     // resident workgroups of each query kernel, by its address (query_resident; 0: a k_shade build that does not fit)
     std::unordered_map<const void*, int> residents;
     // original triangle index -> position in the reference tree's records (ensure_ref_inv: made by the first neighbour,
@@ -3574,6 +3575,47 @@ extern "C" int rt_get_proximity_info(rt_ctx* ctx, rt_proximity_info* info) {
     info->pairs_tested = (long long)c[rtd::PX_PAIRS];
     info->stack_overflows = (long long)c[rtd::PX_ERR];
     return query_finish(ctx, rtq::PROXIMITY, "rt_get_proximity_info", c[rtd::PX_ERR], DEEP_WIDE, &info->kernel_ms);
+}
+
+// ---------------------------------------------------------------- triangle sweep queries (rt_trisweep.hpp)
+extern "C" int rt_sweep_triangles(rt_ctx* ctx, const rt_sweep_tris* r, const rt_trisweep_results* out) {
+    if (!ctx) return RT_E_ARG;
+    if (int rc = rtq::check_enter(rtq::TRISWEEP, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::TRISWEEP, r->kernel, r->n, ctx->err)) return rc;
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->tris || !r->motion)) return arg_err(ctx, "rt_sweep_triangles: null tris / motion");
+    if (r->n > 0 && !out->tri && !out->t && !out->point && !out->kind)
+        return arg_err(ctx, "rt_sweep_triangles: needs a tri, a t, a point or a kind output");
+    rtd::TSArgs A;
+    if (int rc = query_begin(ctx, rtq::TRISWEEP, rtd::TS_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.tris = r->tris;
+    A.motion = r->motion;
+    A.t_max = r->t_max;
+    A.tri = out->tri;
+    A.t = out->t;
+    A.out = out->point;
+    A.kind = out->kind;
+    A.n = r->n;
+    A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::tsw_domain
+    void (*k)(rtd::TSArgs) = r->kernel == RT_KERNEL_STRICT ? rtd::k_trisweep<true> : rtd::k_trisweep<false>;
+    return query_launch(ctx, rtq::TRISWEEP, k, A);
+}
+
+extern "C" int rt_get_trisweep_info(rt_ctx* ctx, rt_trisweep_info* info) {
+    unsigned long long c[rtd::TS_NCOUNT];
+    if (int rc = query_read(ctx, rtq::TRISWEEP, "rt_get_trisweep_info: no triangle sweep query run", c, info)) return rc;
+    info->triangles = (long long)c[rtd::TS_TRIS];
+    info->found = (long long)c[rtd::TS_FOUND];
+    info->empty = (long long)c[rtd::TS_EMPTY];
+    info->walked = (long long)c[rtd::TS_WALKED];
+    info->exhaustive = (long long)c[rtd::TS_EXH];
+    info->nodes_visited = (long long)c[rtd::TS_NODES];
+    info->pairs_gated = (long long)c[rtd::TS_GATED];
+    info->pairs_tested = (long long)c[rtd::TS_PAIRS];
+    info->stack_overflows = (long long)c[rtd::TS_ERR];
+    return query_finish(ctx, rtq::TRISWEEP, "rt_get_trisweep_info", c[rtd::TS_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 namespace {

@@ -1,6 +1,6 @@
-// rt_query_logic.hpp — what the query entry points (rt_trace_rays ... rt_proximity_triangles, rt_hip.hip) decide
+// rt_query_logic.hpp — what the query entry points (rt_trace_rays ... rt_sweep_triangles, rt_hip.hip) decide
 // alike, kept free of HIP so that tests/c/query_logic_test.cpp can check it with g++ alone:
-//   * Fam / FAMILY: the families, and the words in which their messages differ;
+//   * Fam / FAMILY / family(): the families, and the words in which their messages differ;
 //   * check_enter, check_args, check_count_out: the argument checks all of them make, with their messages;
 //   * list_capacity: the list families' kernel capacity for a max_hits / max_tris;
 //   * grid_blocks: the persistent grid of a query launch.
@@ -15,9 +15,12 @@ namespace rtq {
 
 // NFAM counts the ten families that tests/c/query_logic_test.cpp tabulates (its EXPECT[rtq::NFAM] has ten rows and its
 // loops run to NFAM), so it keeps the value 10. A family added since is numbered from NFAM upward; NFAM_ALL ends the
-// list and sizes FAMILY and rt_ctx::slots. Each such family's row has a test of its own (tests/c/proximity_logic_test.cpp).
+// list that tests/c/proximity_logic_test.cpp holds at eleven and sizes FAMILY. Families added after that are numbered
+// from NFAM_ALL upward, have their rows in FAMILY_MORE and end at NFAM_SLOTS, which sizes rt_ctx::slots; family() finds
+// the row of any of them. Each such family's row has a test of its own (tests/c/proximity_logic_test.cpp,
+// tests/c/trisweep_logic_test.cpp).
 enum Fam { RAYS, SHADE, HITS, NEAREST, NEIGHBOURS, OVERLAPS, SWEEP, CONTACTS, CUTS, CLEARANCE, NFAM, PROXIMITY = NFAM,
-           NFAM_ALL };
+           NFAM_ALL, TRISWEEP = NFAM_ALL, NFAM_SLOTS };
 
 struct Family {
     const char* fn;     // the entry point, as its messages begin
@@ -38,27 +41,31 @@ constexpr Family FAMILY[NFAM_ALL] = {
     {"rt_clearance_triangles", "tris", "triangle", nullptr},
     {"rt_proximity_triangles", "tris", "triangle", "max_tris"},
 };
+constexpr Family FAMILY_MORE[NFAM_SLOTS - NFAM_ALL] = {
+    {"rt_sweep_triangles", "tris", "triangle", nullptr},
+};
+constexpr const Family& family(Fam f) { return f < NFAM_ALL ? FAMILY[f] : FAMILY_MORE[f - NFAM_ALL]; }
 
 constexpr int LIST_MAX = 16;  // RT_HITS_MAX, RT_NEIGHBOURS_MAX, ... (rt_hip.hip asserts each)
 
 // Every check returns RT_OK, or the call's status with its message in err (untouched otherwise).
 inline int refuse(int rc, Fam f, const std::string& what, std::string& err) {
-    err = std::string(FAMILY[f].fn) + ": " + what;
+    err = std::string(family(f).fn) + ": " + what;
     return rc;
 }
 
 // the first checks of an entry point: a scene, and both argument structs
 inline int check_enter(Fam f, bool has_scene, bool have_args, std::string& err) {
     if (!has_scene) return refuse(RT_E_STATE, f, "no scene uploaded", err);
-    if (!have_args) return refuse(RT_E_ARG, f, std::string("null ") + FAMILY[f].items + " / results", err);
+    if (!have_args) return refuse(RT_E_ARG, f, std::string("null ") + family(f).items + " / results", err);
     return RT_OK;
 }
 
 // kernel and n; for a list family also its capacity (Family::cap names the field) and count_all
 inline int check_args(Fam f, int kernel, int n, int cap, int count_all, std::string& err) {
     if (kernel < RT_KERNEL_AUTO || kernel > RT_KERNEL_FAST) return refuse(RT_E_ARG, f, "bad kernel", err);
-    if (n < 0) return refuse(RT_E_ARG, f, std::string("negative ") + FAMILY[f].noun + " count", err);
-    const char* field = FAMILY[f].cap;
+    if (n < 0) return refuse(RT_E_ARG, f, std::string("negative ") + family(f).noun + " count", err);
+    const char* field = family(f).cap;
     if (!field) return RT_OK;
     if (cap < 0 || cap > LIST_MAX) return refuse(RT_E_ARG, f, std::string(field) + " must be 0..16", err);
     if (count_all != 0 && count_all != 1) return refuse(RT_E_ARG, f, "count_all must be 0 or 1", err);

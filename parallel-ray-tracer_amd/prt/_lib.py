@@ -313,6 +313,22 @@ class ProximityInfo(ctypes.Structure):  # rt_proximity_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+class SweepTris(ctypes.Structure):  # rt_sweep_tris
+    _fields_ = [("tris", ctypes.c_void_p), ("motion", ctypes.c_void_p), ("t_max", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("kernel", ctypes.c_int)]
+
+
+class TrisweepResults(ctypes.Structure):  # rt_trisweep_results
+    _fields_ = [("tri", ctypes.c_void_p), ("t", ctypes.c_void_p), ("point", ctypes.c_void_p), ("kind", ctypes.c_void_p)]
+
+
+class TrisweepInfo(ctypes.Structure):  # rt_trisweep_info
+    _fields_ = [("triangles", ctypes.c_longlong), ("found", ctypes.c_longlong), ("empty", ctypes.c_longlong),
+                ("walked", ctypes.c_longlong), ("exhaustive", ctypes.c_longlong), ("nodes_visited", ctypes.c_longlong),
+                ("pairs_gated", ctypes.c_longlong), ("pairs_tested", ctypes.c_longlong),
+                ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -450,6 +466,8 @@ def hip():
         L.rt_get_clearance_info.argtypes = [ctypes.c_void_p, P(ClearanceInfo)]
         L.rt_proximity_triangles.argtypes = [ctypes.c_void_p, P(ProxTris), P(ProximityResults)]
         L.rt_get_proximity_info.argtypes = [ctypes.c_void_p, P(ProximityInfo)]
+        L.rt_sweep_triangles.argtypes = [ctypes.c_void_p, P(SweepTris), P(TrisweepResults)]
+        L.rt_get_trisweep_info.argtypes = [ctypes.c_void_p, P(TrisweepInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

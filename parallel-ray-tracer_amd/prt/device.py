@@ -960,6 +960,62 @@ class Renderer:
         stack"""
         return self._info(_lib.ClearanceInfo, "rt_get_clearance_info")
 
+    def sweep_tris(self, tris, motions, t_max=None, kernel="fast", kind=None, tri=None, t=None, point=None):
+        """rt_sweep_triangles: per moving triangle -- corners q + t d at time t, no rotation -- its first contact with
+        the scene: the first triangle by (toi, original triangle index), whatever the BVH (include/rt_hip.h states toi:
+        a box-against-box gate, cuts' X where the gate opens, then three query-corner, three mesh-corner and nine
+        edge-pair candidates) -> (tri [n] int32, -1 when nothing is touched within the bound; t [n] float32 = toi,
+        FLT_MAX then; point [n, 3] float32 = the contact point on the mesh triangle, q0's own bits then). tris: an
+        [n, 3, 3] float32 contiguous tensor on this device (or a raw pointer: tris=(pointer, n), with motions a raw
+        pointer too); motions: [n, 3] float32, not normalised, and d = 0 asks "does it touch now"; a non-finite number
+        in either gives the empty set. t_max: optional [n] float32 tensor of bounds on t (+inf: none; 0: touching now;
+        NaN or negative: nothing). kind: an optional [n] int32 output that receives the winning candidate (0..2 a query
+        corner, 3..5 a mesh corner, 6..14 an edge pair, 15 a start in contact, -1 the empty set). kernel="strict" runs
+        every query against every triangle (the checker), "fast" / "auto" walks the full wide view with the same bits.
+        tri / t / point: optional outputs (allocated when not given). Asynchronous on the renderer's stream: sync() or
+        trisweep_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if isinstance(tris, tuple):
+            if not isinstance(motions, int):
+                raise RtError("motions: a raw pointer goes with tris=(pointer, n)")
+        else:
+            if not isinstance(motions, torch.Tensor):
+                raise RtError(f"motions: expected a torch tensor, got {type(motions).__name__}")
+            if motions.dim() != 2 or motions.shape[1] != 3:
+                raise RtError(f"motions: shape {tuple(motions.shape)}, expected [n, 3]")
+        pt, n = self._tris(tris)
+        pd = _ptr(motions, "motions", 3 * n, f32, self.device)
+        if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
+            raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
+        if t_max is not None and not isinstance(t_max, (torch.Tensor, int)):
+            raise RtError(f"t_max: expected a torch tensor, got {type(t_max).__name__}")
+        if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
+        pm = _ptr(t_max, "t_max", n, f32, self.device)
+        for x, what, m, dt in ((tri, "tri", n, i32), (t, "t", n, f32), (point, "point", 3 * n, f32),
+                               (kind, "kind", n, i32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty(n, dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+        if point is None:
+            point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        res = _lib.TrisweepResults(_ptr(tri, "tri", n, i32, self.device), _ptr(t, "t", n, f32, self.device),
+                                   _ptr(point, "point", 3 * n, f32, self.device),
+                                   _ptr(kind, "kind", n, i32, self.device))
+        q = _lib.SweepTris(pt, pd, pm, n, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_sweep_triangles(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_sweep_triangles")
+        return tri, t, point
+
+    def trisweep_info(self):
+        """rt_get_trisweep_info: the last triangle sweep query's counters (triangles, found, empty, walked, exhaustive,
+        nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed its
+        stack"""
+        return self._info(_lib.TrisweepInfo, "rt_get_trisweep_info")
+
     def _max_dist2(self, max_dist2, n):
         """the pointer of an optional [n] float32 tensor of squared bounds, checked as clearance checks it"""
         import torch
