@@ -1114,6 +1114,83 @@ typedef struct rt_trisweep_info {
  * are not valid), RT_E_STATE before the first */
 int rt_get_trisweep_info(rt_ctx* ctx, rt_trisweep_info* info);
 
+/* Triangle contact queries: per caller-supplied moving triangle the k earliest contacts with the mesh and the number of
+ * contacts -- rt_sweep_triangles' plural form, as rt_sweep_contacts is rt_sweep_spheres' (every mesh triangle that
+ * shares the touched edge or corner: they tie at one time of impact; every triangle a face already touches where it
+ * starts, to be pushed out of; the sheets behind the first one; the number of mesh triangles that the swept volume of
+ * the face touches).
+ * Query i is rt_sweep_triangles' own: corners q + t d over 0 <= t <= T = fminf(t_max[i], FLT_MAX). Its candidate set is
+ * the sweep's own, in the sweep's order:
+ *   S_i = { j : toi(i, triangle j) exists and toi <= T }, ordered by (toi ascending, original index ascending),
+ * and it is empty under the sweep's rules, decided before any walk: a non-finite one among the twelve numbers of q0,
+ * q1, q2, d, or a NaN or negative t_max[i], the sign read from the bits. toi, the contact point and the kind of a pair
+ * are steps 1-6 of rt_sweep_triangles above, not restated here.
+ * A pair's toi, point and kind depend on the query and the triangle alone: not on the bound (T enters the gate as the
+ * first value of the interval's end t1 and the last comparison toi <= T, and nothing else reads either), and not on any
+ * other member of S_i. The form rests on this: a member has the same bits at every max_tris, with and without
+ * count_all, under every bound that keeps it, and in rt_sweep_triangles' own answer.
+ * Results, for max_tris (k) in 0..RT_TRICONTACTS_MAX; the slots past |S_i| of query i are its unused slots:
+ *   tri   [n][k]     the first k entries of S_i; -1 in unused slots
+ *   t     [n][k]     their toi; FLT_MAX in unused slots
+ *   point [n][k][3]  each pair's own contact point (step 6); q0's own bits in unused slots
+ *   kind  [n][k]     each pair's own kind, 0..15; -1 in unused slots
+ *   count [n]        min(|S_i|, k), or |S_i| itself with count_all
+ * max_tris = 0 needs count_all and a count pointer and is the pure count; with t_max = 1 it is the number of mesh
+ * triangles that the prism swept from q to q + d touches. With max_tris = 1 and no count_all, tri, t, point and kind
+ * are rt_sweep_triangles' answer bit for bit.
+ * Not promised: a t_max = 0 or d = 0 set is not rt_cut_triangles' set, nor rt_proximity_triangles' set at bound 0 -- the
+ * gate and the touching candidates differ from those queries' tests by rounding.
+ * Documented, not fixed, as for rt_sweep_triangles: motion inside the common plane of a coplanar pair and contacts of
+ * exactly parallel edges give no member; a query of zero area is answered by the candidates alone; membership at a
+ * grazing contact is exact only to rounding; coordinates whose triple products overflow float32 (beyond about 2^42)
+ * give the empty set.
+ * RT_KERNEL_STRICT runs every query against every triangle under T (the checker); RT_KERNEL_FAST walks the full 8-wide
+ * view, slots in order of their gate t0, pruned by lim = fminf(T, the k-th stored toi once the list is full) -- T alone
+ * with count_all -- and answers with the same bits. A scene without a wide view and, under
+ * RT_KERNEL_FAST, a query outside rt_sweep_triangles' walk domain run the exhaustive loop.
+ * A triangle contact query touches nothing a render or any other query owns. */
+#define RT_TRICONTACTS_MAX 16
+typedef struct rt_tri_contacts {
+    const float* tris;   /* device, [n][3][3] f32: q0, q1, q2 of every query */
+    const float* motion; /* device, [n][3] f32: d, not normalised */
+    const float* t_max;  /* device, [n] f32, nullable (NULL or +inf: no bound) */
+    int n;               /* >= 0; 0 is RT_OK and launches nothing */
+    int max_tris;        /* 0..RT_TRICONTACTS_MAX */
+    int count_all;       /* 0 / 1: count holds |S_i| itself */
+    int kernel;          /* RT_KERNEL_AUTO (= FAST) / STRICT / FAST */
+} rt_tri_contacts;
+typedef struct rt_tricontact_results { /* device pointers, all nullable */
+    int* tri;     /* [n][max_tris] */
+    float* t;     /* [n][max_tris] */
+    float* point; /* [n][max_tris][3] */
+    int* kind;    /* [n][max_tris] */
+    int* count;   /* [n] */
+} rt_tricontact_results;
+/* asynchronous on the context stream; elements at index n and beyond are not written. RT_E_STATE before an upload;
+ * RT_E_ARG for a null struct, null tris or motion with n > 0, max_tris outside 0..RT_TRICONTACTS_MAX, max_tris > 0 with
+ * tri, t, point and kind all NULL (whatever count is), max_tris = 0 without count_all and a count pointer, count_all not
+ * 0 or 1, an unknown kernel, a negative n. */
+int rt_sweep_tri_contacts(rt_ctx* ctx, const rt_tri_contacts* tris, const rt_tricontact_results* out);
+typedef struct rt_tricontacts_info {
+    long long triangles, found; /* found: query triangles with a non-empty S_i */
+    long long stored;           /* list entries written (sum of min(|S_i|, max_tris)) */
+    long long counted;          /* sum of the count output (whether or not it was asked for) */
+    long long walked;           /* query triangles that walked the wide view */
+    long long exhaustive;       /* query triangles run against every triangle: all valid ones under RT_KERNEL_STRICT or
+                                   without a wide view, and those outside the walk's domain (an invalid one is in neither) */
+    long long empty;            /* triangles - found */
+    long long nodes_visited;    /* wide nodes decoded, summed over the queries (a level popped again counts again) */
+    long long pairs_gated;      /* the walk: triangles of a visited leaf slot turned away by their own gate (0 in the
+                                   exhaustive loop) */
+    long long pairs_tested;     /* the walk: triangles past their own gate; exhaustive: queries x triangles; the second
+                                   evaluation that fills point and kind is not counted */
+    long long stack_overflows;  /* must be 0 */
+    float kernel_ms;            /* HIP events around the query's launch */
+} rt_tricontacts_info;
+/* counters of the last triangle contact query (synchronises); RT_E_KERNEL when it overflowed the walk's stack (its
+ * results are not valid), RT_E_STATE before the first */
+int rt_get_tricontacts_info(rt_ctx* ctx, rt_tricontacts_info* info);
+
 /* Vertex updates: moving geometry without a new upload. Every view of the uploaded scene -- the reference tree of the
  * strict walk, the binary acceleration view where one exists, the 8-wide full / unit / primary views, the triangle
  * records, the shading normals, the box-face lists -- is refitted on the device to the new coordinates; topology stays.

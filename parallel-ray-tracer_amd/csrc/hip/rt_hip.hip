@@ -46,6 +46,7 @@
 #include "rt_clearance.hpp"
 #include "rt_proximity.hpp"
 #include "rt_trisweep.hpp"
+#include "rt_tricontacts.hpp"
 #include "rt_refit.hpp"
 #include "rt_collapse.hpp"
 #ifndef PRT_TREELET
@@ -240,11 +241,11 @@ struct rt_ctx {
         unsigned long long* counters = nullptr;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool run = false, launched = false;
-    } slots[rtq::NFAM_SLOTS];
+    } slots[rtq::NFAM_END];
     // resident workgroups of each query kernel, by its address (query_resident; 0: a k_shade build that does not fit)
     std::unordered_map<const void*, int> residents;
     // original triangle index -> position in the reference tree's records (ensure_ref_inv: made by the first neighbour,
-    // contact or proximity query of a scene that asks for points, freed with the scene)
+    // contact, proximity or triangle contact query of a scene that asks for points, freed with the scene)
     int* d_ref_inv = nullptr;
     // RT_VARIANT_HYBRID (single 1-spp frames), keyed by the frame's SHAPE: the per-tile times of a measuring k_persist
     // frame, the candidates' tile lists they give (the hot kernel's tiles of the costliest 8x8 tiles; the rest for the
@@ -3616,6 +3617,60 @@ extern "C" int rt_get_trisweep_info(rt_ctx* ctx, rt_trisweep_info* info) {
     info->pairs_tested = (long long)c[rtd::TS_PAIRS];
     info->stack_overflows = (long long)c[rtd::TS_ERR];
     return query_finish(ctx, rtq::TRISWEEP, "rt_get_trisweep_info", c[rtd::TS_ERR], DEEP_WIDE, &info->kernel_ms);
+}
+
+// ---------------------------------------------------------------- triangle contact queries (rt_tricontacts.hpp)
+extern "C" int rt_sweep_tri_contacts(rt_ctx* ctx, const rt_tri_contacts* r, const rt_tricontact_results* out) {
+    static_assert(RT_TRICONTACTS_MAX == rtd::TRICONTACTS_MAX && RT_TRICONTACTS_MAX == rtq::LIST_MAX,
+                  "rt_hip.h, rt_tricontacts.hpp and rt_query_logic.hpp must agree");
+    if (!ctx) return RT_E_ARG;
+    if (int rc = rtq::check_enter(rtq::TRICONTACTS, ctx->has_scene, r && out, ctx->err)) return rc;
+    if (int rc = rtq::check_args(rtq::TRICONTACTS, r->kernel, r->n, r->max_tris, r->count_all, ctx->err)) return rc;
+    // (n = 0 reads and writes nothing: empty arrays may have no address)
+    if (r->n > 0 && (!r->tris || !r->motion)) return arg_err(ctx, "rt_sweep_tri_contacts: null tris / motion");
+    if (r->n > 0 && r->max_tris > 0 && !out->tri && !out->t && !out->point && !out->kind)
+        return arg_err(ctx, "rt_sweep_tri_contacts: max_tris > 0 needs a tri, a t, a point or a kind output");
+    if (int rc = rtq::check_count_out(rtq::TRICONTACTS, r->n, r->max_tris, out->count != nullptr, ctx->err)) return rc;
+    rtd::TCArgs A;
+    if (int rc = query_begin(ctx, rtq::TRICONTACTS, rtd::TC_NCOUNT, A)) return rc;
+    if (r->n == 0) return RT_OK;
+    const bool lists = r->max_tris > 0;
+    if (lists && (out->point || out->kind))
+        if (int rc = ensure_ref_inv(ctx)) return rc;
+    A.s = scene_args(ctx);  // (the full wide view only; without one the kernel runs its exhaustive loop)
+    A.tris = r->tris;
+    A.motion = r->motion;
+    A.t_max = r->t_max;
+    A.tri = lists ? out->tri : nullptr;
+    A.t = lists ? out->t : nullptr;
+    A.out = lists ? out->point : nullptr;
+    A.kind = lists ? out->kind : nullptr;
+    A.count = out->count;
+    A.ref_inv = ctx->d_ref_inv;
+    A.n = r->n;
+    A.c_max = std::ldexp(ctx->scene_mx, 20);  // rtd::tsw_domain
+    A.max_tris = r->max_tris;
+    A.count_all = r->count_all;
+    return query_launch(ctx, rtq::TRICONTACTS,
+                        FOR_LIST_CAP(r->max_tris, r->kernel == RT_KERNEL_STRICT, rtd::k_tricontacts), A);
+}
+
+extern "C" int rt_get_tricontacts_info(rt_ctx* ctx, rt_tricontacts_info* info) {
+    unsigned long long c[rtd::TC_NCOUNT];
+    if (int rc = query_read(ctx, rtq::TRICONTACTS, "rt_get_tricontacts_info: no triangle contact query run", c, info))
+        return rc;
+    info->triangles = (long long)c[rtd::TC_TRIS];
+    info->found = (long long)c[rtd::TC_FOUND];
+    info->stored = (long long)c[rtd::TC_STORED];
+    info->counted = (long long)c[rtd::TC_COUNTED];
+    info->walked = (long long)c[rtd::TC_WALKED];
+    info->exhaustive = (long long)c[rtd::TC_EXH];
+    info->empty = (long long)c[rtd::TC_EMPTY];
+    info->nodes_visited = (long long)c[rtd::TC_NODES];
+    info->pairs_gated = (long long)c[rtd::TC_GATED];
+    info->pairs_tested = (long long)c[rtd::TC_PAIRS];
+    info->stack_overflows = (long long)c[rtd::TC_ERR];
+    return query_finish(ctx, rtq::TRICONTACTS, "rt_get_tricontacts_info", c[rtd::TC_ERR], DEEP_WIDE, &info->kernel_ms);
 }
 
 namespace {

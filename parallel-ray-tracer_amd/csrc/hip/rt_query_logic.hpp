@@ -1,4 +1,4 @@
-// rt_query_logic.hpp — what the query entry points (rt_trace_rays ... rt_sweep_triangles, rt_hip.hip) decide
+// rt_query_logic.hpp — what the query entry points (rt_trace_rays ... rt_sweep_tri_contacts, rt_hip.hip) decide
 // alike, kept free of HIP so that tests/c/query_logic_test.cpp can check it with g++ alone:
 //   * Fam / FAMILY / family(): the families, and the words in which their messages differ;
 //   * check_enter, check_args, check_count_out: the argument checks all of them make, with their messages;
@@ -19,8 +19,14 @@ namespace rtq {
 // from NFAM_ALL upward, have their rows in FAMILY_MORE and end at NFAM_SLOTS, which sizes rt_ctx::slots; family() finds
 // the row of any of them. Each such family's row has a test of its own (tests/c/proximity_logic_test.cpp,
 // tests/c/trisweep_logic_test.cpp).
+// tests/c/trisweep_logic_test.cpp in turn holds NFAM_SLOTS at 12 and FAMILY_MORE at NFAM_SLOTS - NFAM_ALL rows, so
+// families added after it are numbered from NFAM_SLOTS upward (TRICONTACTS = NFAM_SLOTS), have their rows in
+// FAMILY_LATER and end at NFAM_END, which sizes rt_ctx::slots. This is the last table: tests/c/tricontacts_logic_test.cpp
+// asserts its family's number, its row's words and its messages, and neither NFAM_END's value nor FAMILY_LATER's row
+// count, so the next family appends its enumerator before NFAM_END and its row to FAMILY_LATER, and writes its own
+// test the same way.
 enum Fam { RAYS, SHADE, HITS, NEAREST, NEIGHBOURS, OVERLAPS, SWEEP, CONTACTS, CUTS, CLEARANCE, NFAM, PROXIMITY = NFAM,
-           NFAM_ALL, TRISWEEP = NFAM_ALL, NFAM_SLOTS };
+           NFAM_ALL, TRISWEEP = NFAM_ALL, NFAM_SLOTS, TRICONTACTS = NFAM_SLOTS, NFAM_END };
 
 struct Family {
     const char* fn;     // the entry point, as its messages begin
@@ -44,7 +50,12 @@ constexpr Family FAMILY[NFAM_ALL] = {
 constexpr Family FAMILY_MORE[NFAM_SLOTS - NFAM_ALL] = {
     {"rt_sweep_triangles", "tris", "triangle", nullptr},
 };
-constexpr const Family& family(Fam f) { return f < NFAM_ALL ? FAMILY[f] : FAMILY_MORE[f - NFAM_ALL]; }
+constexpr Family FAMILY_LATER[NFAM_END - NFAM_SLOTS] = {
+    {"rt_sweep_tri_contacts", "tris", "triangle", "max_tris"},
+};
+constexpr const Family& family(Fam f) {
+    return f < NFAM_ALL ? FAMILY[f] : f < NFAM_SLOTS ? FAMILY_MORE[f - NFAM_ALL] : FAMILY_LATER[f - NFAM_SLOTS];
+}
 
 constexpr int LIST_MAX = 16;  // RT_HITS_MAX, RT_NEIGHBOURS_MAX, ... (rt_hip.hip asserts each)
 

@@ -329,6 +329,27 @@ class TrisweepInfo(ctypes.Structure):  # rt_trisweep_info
                 ("stack_overflows", ctypes.c_longlong), ("kernel_ms", ctypes.c_float)]
 
 
+TRICONTACTS_MAX = 16  # RT_TRICONTACTS_MAX
+
+
+class TriContacts(ctypes.Structure):  # rt_tri_contacts
+    _fields_ = [("tris", ctypes.c_void_p), ("motion", ctypes.c_void_p), ("t_max", ctypes.c_void_p), ("n", ctypes.c_int),
+                ("max_tris", ctypes.c_int), ("count_all", ctypes.c_int), ("kernel", ctypes.c_int)]
+
+
+class TricontactResults(ctypes.Structure):  # rt_tricontact_results
+    _fields_ = [("tri", ctypes.c_void_p), ("t", ctypes.c_void_p), ("point", ctypes.c_void_p), ("kind", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
+
+class TricontactsInfo(ctypes.Structure):  # rt_tricontacts_info
+    _fields_ = [("triangles", ctypes.c_longlong), ("found", ctypes.c_longlong), ("stored", ctypes.c_longlong),
+                ("counted", ctypes.c_longlong), ("walked", ctypes.c_longlong), ("exhaustive", ctypes.c_longlong),
+                ("empty", ctypes.c_longlong), ("nodes_visited", ctypes.c_longlong), ("pairs_gated", ctypes.c_longlong),
+                ("pairs_tested", ctypes.c_longlong), ("stack_overflows", ctypes.c_longlong),
+                ("kernel_ms", ctypes.c_float)]
+
+
 class VertexUpdate(ctypes.Structure):  # rt_vertex_update
     _fields_ = [("coords", ctypes.c_void_p), ("n_triangles", ctypes.c_int)]
 
@@ -468,6 +489,8 @@ def hip():
         L.rt_get_proximity_info.argtypes = [ctypes.c_void_p, P(ProximityInfo)]
         L.rt_sweep_triangles.argtypes = [ctypes.c_void_p, P(SweepTris), P(TrisweepResults)]
         L.rt_get_trisweep_info.argtypes = [ctypes.c_void_p, P(TrisweepInfo)]
+        L.rt_sweep_tri_contacts.argtypes = [ctypes.c_void_p, P(TriContacts), P(TricontactResults)]
+        L.rt_get_tricontacts_info.argtypes = [ctypes.c_void_p, P(TricontactsInfo)]
         L.rt_update_vertices.argtypes = [ctypes.c_void_p, P(VertexUpdate)]
         L.rt_get_update_info.argtypes = [ctypes.c_void_p, P(UpdateInfo)]
         L.rt_update_lights.argtypes = [ctypes.c_void_p, P(Light), ctypes.c_int]

@@ -960,6 +960,26 @@ class Renderer:
         stack"""
         return self._info(_lib.ClearanceInfo, "rt_get_clearance_info")
 
+    def _moving_tris(self, tris, motions, t_max):
+        """the pointers of a triangle sweep's query triangles and motions and their count, checked as sweep_tris checks
+        them, t_max's kind and shape included (its pointer is taken by the caller, after its own shape checks)"""
+        import torch
+        if isinstance(tris, tuple):
+            if not isinstance(motions, int):
+                raise RtError("motions: a raw pointer goes with tris=(pointer, n)")
+        else:
+            if not isinstance(motions, torch.Tensor):
+                raise RtError(f"motions: expected a torch tensor, got {type(motions).__name__}")
+            if motions.dim() != 2 or motions.shape[1] != 3:
+                raise RtError(f"motions: shape {tuple(motions.shape)}, expected [n, 3]")
+        pt, n = self._tris(tris)
+        pd = _ptr(motions, "motions", 3 * n, (torch.float32,), self.device)
+        if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
+            raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
+        if t_max is not None and not isinstance(t_max, (torch.Tensor, int)):
+            raise RtError(f"t_max: expected a torch tensor, got {type(t_max).__name__}")
+        return pt, n, pd
+
     def sweep_tris(self, tris, motions, t_max=None, kernel="fast", kind=None, tri=None, t=None, point=None):
         """rt_sweep_triangles: per moving triangle -- corners q + t d at time t, no rotation -- its first contact with
         the scene: the first triangle by (toi, original triangle index), whatever the BVH (include/rt_hip.h states toi:
@@ -976,20 +996,7 @@ class Renderer:
         trisweep_info() before the results are read on another stream."""
         import torch
         f32, i32 = (torch.float32,), (torch.int32,)
-        if isinstance(tris, tuple):
-            if not isinstance(motions, int):
-                raise RtError("motions: a raw pointer goes with tris=(pointer, n)")
-        else:
-            if not isinstance(motions, torch.Tensor):
-                raise RtError(f"motions: expected a torch tensor, got {type(motions).__name__}")
-            if motions.dim() != 2 or motions.shape[1] != 3:
-                raise RtError(f"motions: shape {tuple(motions.shape)}, expected [n, 3]")
-        pt, n = self._tris(tris)
-        pd = _ptr(motions, "motions", 3 * n, f32, self.device)
-        if isinstance(t_max, torch.Tensor) and t_max.dim() != 1:
-            raise RtError(f"t_max: shape {tuple(t_max.shape)}, expected [n]")
-        if t_max is not None and not isinstance(t_max, (torch.Tensor, int)):
-            raise RtError(f"t_max: expected a torch tensor, got {type(t_max).__name__}")
+        pt, n, pd = self._moving_tris(tris, motions, t_max)
         if isinstance(point, torch.Tensor) and (point.dim() != 2 or point.shape[1] != 3):
             raise RtError(f"point: shape {tuple(point.shape)}, expected [n, 3]")
         pm = _ptr(t_max, "t_max", n, f32, self.device)
@@ -1015,6 +1022,60 @@ class Renderer:
         nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when the query overflowed its
         stack"""
         return self._info(_lib.TrisweepInfo, "rt_get_trisweep_info")
+
+    def sweep_tri_contacts(self, tris, motions, k=8, t_max=None, count_all=False, points_out=False, kernel="auto",
+                           tri=None, t=None, count=None, point=None, kind=None):
+        """rt_sweep_tri_contacts: per moving triangle its k earliest contacts with the scene -- the first k by (toi,
+        original triangle index) among the triangles with toi <= t_max, sweep_tris' own set and order
+        (include/rt_hip.h) -> (tri [n, k] int32, -1 in unused slots; t [n, k] float32 = each contact's toi, FLT_MAX in
+        unused slots; count [n] int32 = min(contacts within the bound, k), or every contact within the bound with
+        count_all=True, when the walk prunes at the bound only), plus point [n, k, 3] float32 (each contact's own
+        contact point on its mesh triangle; q0's own bits in unused slots) with points_out=True or a `point` output.
+        kind: an optional [n, k] int32 output that receives each entry's winning candidate (0..15; -1 in unused slots).
+        k: 0..16; 0 with count_all=True is a pure count (tri and t come back empty) -- with t_max = 1 the number of
+        triangles the prism swept from q to q + d touches. With k = 1 the answer is sweep_tris', bit for bit. tris,
+        motions, t_max and kernel as sweep_tris takes them; without a bound count_all counts every triangle the face
+        ever touches. tri / t / count / point: optional outputs (allocated when not given). Asynchronous on the
+        renderer's stream: sync() or tricontacts_info() before the results are read on another stream."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.int32,)
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k <= _lib.TRICONTACTS_MAX:
+            raise RtError(f"k: {k!r}, expected an int in 0..{_lib.TRICONTACTS_MAX}")
+        if k == 0 and not count_all:
+            raise RtError("k = 0 stores nothing: it needs count_all=True")
+        pt, n, pd = self._moving_tris(tris, motions, t_max)
+        for x, what in ((tri, "tri"), (t, "t"), (kind, "kind")):
+            if isinstance(x, torch.Tensor) and (x.dim() != 2 or x.shape[1] != k):
+                raise RtError(f"{what}: shape {tuple(x.shape)}, expected [n, k]")
+        if isinstance(point, torch.Tensor) and (point.dim() != 3 or tuple(point.shape[1:]) != (k, 3)):
+            raise RtError(f"point: shape {tuple(point.shape)}, expected [n, {k}, 3]")
+        pm = _ptr(t_max, "t_max", n, f32, self.device)
+        for x, what, m, dt in ((tri, "tri", n * k, i32), (t, "t", n * k, f32), (count, "count", n, i32),
+                               (point, "point", 3 * n * k, f32), (kind, "kind", n * k, i32)):
+            _ptr(x, what, m, dt, self.device)  # (the caller's outputs are checked before anything is allocated)
+        dev = f"cuda:{self.device}"
+        if tri is None:
+            tri = torch.empty((n, k), dtype=torch.int32, device=dev)
+        if t is None:
+            t = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if count is None:
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+        if point is None and points_out:
+            point = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        res = _lib.TricontactResults(_ptr(tri, "tri", n * k, i32, self.device) if k else None,
+                                     _ptr(t, "t", n * k, f32, self.device) if k else None,
+                                     _ptr(point, "point", 3 * n * k, f32, self.device) if k else None,
+                                     _ptr(kind, "kind", n * k, i32, self.device) if k else None,
+                                     _ptr(count, "count", n, i32, self.device))
+        q = _lib.TriContacts(pt, pd, pm, n, k, 1 if count_all else 0, KERNELS.get(kernel, kernel))
+        self._chk(_L.rt_sweep_tri_contacts(self._ctx, ctypes.byref(q), ctypes.byref(res)), "rt_sweep_tri_contacts")
+        return (tri, t, count) if point is None else (tri, t, count, point)
+
+    def tricontacts_info(self):
+        """rt_get_tricontacts_info: the last triangle contact query's counters (triangles, found, stored, counted,
+        walked, exhaustive, empty, nodes_visited, pairs_gated, pairs_tested) and kernel_ms; synchronises; raises when
+        the query overflowed its stack"""
+        return self._info(_lib.TricontactsInfo, "rt_get_tricontacts_info")
 
     def _max_dist2(self, max_dist2, n):
         """the pointer of an optional [n] float32 tensor of squared bounds, checked as clearance checks it"""

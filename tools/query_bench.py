@@ -34,8 +34,11 @@ usage: python tools/query_bench.py [--scenes dragon car_boxed] [--width 1920 --h
        python tools/query_bench.py --mode clearance [--runs 5] [--out profiles/clearance_bench_<md5>.jsonl]
        python tools/query_bench.py --mode proximity [--runs 3] [--out profiles/proximity_bench_<md5>.jsonl]
        python tools/query_bench.py --mode trisweep [--runs 5] [--out profiles/trisweep_bench_<md5>.jsonl]
+       python tools/query_bench.py --mode tricontacts [--runs 3] [--out profiles/tricontacts_bench_<md5>.jsonl]
 --mode trisweep times rt_sweep_triangles beside rt_sweep_spheres with r = 0 on the same centres and motions and beside
-rt_clearance_triangles on the same triangles (trisweep_mode below)."""
+rt_clearance_triangles on the same triangles (trisweep_mode below). --mode tricontacts times
+rt_sweep_tri_contacts' lists and its swept-volume count beside rt_sweep_triangles on the same queries (tricontacts_mode
+below)."""
 import argparse
 import json
 import os
@@ -53,7 +56,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--mode", choices=["trace", "shade", "hits", "nearest", "neighbours", "overlap", "sweep", "cuts",
-                                       "contacts", "clearance", "proximity", "trisweep"],
+                                       "contacts", "clearance", "proximity", "trisweep", "tricontacts"],
                     default="trace",
                     help="trace: rt_trace_rays (above); shade: rt_shade_rays' forms beside rt_render (shade_mode); "
                          "hits: rt_trace_hits beside the closest-hit query (hits_mode); "
@@ -68,7 +71,9 @@ def main():
                          "proximity: rt_proximity_triangles beside rt_clearance_triangles and rt_cut_triangles' count "
                          "(proximity_mode); "
                          "trisweep: rt_sweep_triangles beside rt_sweep_spheres at r = 0 and rt_clearance_triangles "
-                         "(trisweep_mode)")
+                         "(trisweep_mode); "
+                         "tricontacts: rt_sweep_tri_contacts' lists and swept-volume count beside rt_sweep_triangles "
+                         "(tricontacts_mode)")
     ap.add_argument("--out", default=None,
                     help="nearest, neighbours, overlap, sweep, cuts, contacts: also append the raw lines to this file")
     ap.add_argument("--regroups", type=int, nargs="+", default=[4, 16, 32], help="shade: the pool form's thresholds")
@@ -100,6 +105,8 @@ def main():
         return proximity_mode(a, md5)
     if a.mode == "trisweep":
         return trisweep_mode(a, md5)
+    if a.mode == "tricontacts":
+        return tricontacts_mode(a, md5)
     for name in a.scenes:
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
@@ -1009,6 +1016,37 @@ def proximity_mode(a, md5):
         out.close()
 
 
+def moving_triangle_sets(r, s, W, H, NS):
+    """trisweep_mode's query sets (its docstring), one after another -> (pct, "ray" / "surface", size, the centres
+    [n, 3], the triangles [n, 3, 3], the motions [n, 3], t_max [n] or None, (the same three for NS of the queries))"""
+    import numpy as np
+    import torch
+    n = W * H
+    o, d, g, _ = point_sets(r, s, W, H)
+    hit, t = r.trace_rays(o, d, kernel="fast")
+    r.sync()
+    t = torch.where(hit >= 0, t, torch.ones_like(t))
+    v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
+    ext = float((v.max(0) - v.min(0)).max())
+    off = torch.randn(n, 3, 3, generator=g)
+    off = (off - off.mean(dim=1, keepdim=True)).cuda()
+    w = d / d.norm(dim=1, keepdim=True)
+    up = torch.tensor([0.0, 1.0, 0.0], device="cuda").expand_as(w)
+    side = torch.linalg.cross(w, up)
+    side = side / side.norm(dim=1, keepdim=True).clamp_min(1e-6)
+    for pct in (0.1, 1.0, 5.0):
+        size = ext * pct / 100
+        for what in ("ray", "surface"):
+            back = 3.0 * size + (0.05 * ext if what == "ray" else 0.0)
+            ctr = (o + w * (t * d.norm(dim=1) - back)[:, None]).contiguous()
+            q = (ctr[:, None, :] + off * size).contiguous()
+            mv = ((w if what == "ray" else side) * (0.1 * ext)).contiguous()
+            tm = None if what == "ray" else torch.ones(n, dtype=torch.float32, device="cuda")
+            pick = torch.randperm(n, generator=g)[:NS].cuda()
+            sample = (q[pick].contiguous(), mv[pick].contiguous(), None if tm is None else tm[pick].contiguous())
+            yield pct, what, size, ctr, q, mv, tm, sample
+
+
 def trisweep_mode(a, md5):
     """--mode trisweep: per scene, rt_sweep_triangles on W x H query triangles (1920 x 1080 by default):
     cuts_mode's triangles of 0.1 %, 1 % and 5 % of the scene's extent, centred on the camera's primary rays, in two
@@ -1032,79 +1070,142 @@ def trisweep_mode(a, md5):
         s = host.Scene.named(name).build_bvh(3)
         r = device.Renderer(0)
         r.upload(s)
-        o, d, g, _ = point_sets(r, s, W, H)
-        hit, t = r.trace_rays(o, d, kernel="fast")
-        r.sync()
-        t = torch.where(hit >= 0, t, torch.ones_like(t))
-        v = np.ascontiguousarray(s.triangles["coords"], np.float32).reshape(-1, 3)
-        ext = float((v.max(0) - v.min(0)).max())
-        off = torch.randn(n, 3, 3, generator=g)
-        off = (off - off.mean(dim=1, keepdim=True)).cuda()
-        w = d / d.norm(dim=1, keepdim=True)
-        up = torch.tensor([0.0, 1.0, 0.0], device="cuda").expand_as(w)
-        side = torch.linalg.cross(w, up)
-        side = side / side.norm(dim=1, keepdim=True).clamp_min(1e-6)
-        for pct in (0.1, 1.0, 5.0):
-            size = ext * pct / 100
-            for what in ("ray", "surface"):
-                back = 3.0 * size + (0.05 * ext if what == "ray" else 0.0)
-                ctr = (o + w * (t * d.norm(dim=1) - back)[:, None]).contiguous()
-                q = (ctr[:, None, :] + off * size).contiguous()
-                mv = ((w if what == "ray" else side) * (0.1 * ext)).contiguous()
-                tm = None if what == "ray" else torch.ones(n, dtype=torch.float32, device="cuda")
-                pick = torch.randperm(n, generator=g)[:NS].cuda()
-                qs, ms_, ts = q[pick].contiguous(), mv[pick].contiguous(), None if tm is None else tm[pick].contiguous()
-                kind = torch.empty(n, dtype=torch.int32, device="cuda")
-                torch.cuda.synchronize()
+        for pct, what, size, ctr, q, mv, tm, (qs, ms_, ts) in moving_triangle_sets(r, s, W, H, NS):
+            kind = torch.empty(n, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
 
-                def trisweep(p=q, m=mv, b=tm, kernel="fast", kd=None):
-                    res = r.sweep_tris(p, m, t_max=b, kernel=kernel, kind=kd)
-                    return r.trisweep_info(), res, len(p)
+            def trisweep(p=q, m=mv, b=tm, kernel="fast", kd=None):
+                res = r.sweep_tris(p, m, t_max=b, kernel=kernel, kind=kd)
+                return r.trisweep_info(), res, len(p)
 
-                def sphere():
-                    res = r.sweep(ctr, mv, 0.0, t_max=tm)
-                    return r.sweep_info(), res, n
+            def sphere():
+                res = r.sweep(ctr, mv, 0.0, t_max=tm)
+                return r.sweep_info(), res, n
 
-                def clearance():
-                    res = r.clearance(q)
-                    return r.clearance_info(), res, n
+            def clearance():
+                res = r.clearance(q)
+                return r.clearance_info(), res, n
 
-                arms = [("trisweep", lambda: trisweep(kd=kind)), ("sweep_r0", sphere), ("clearance", clearance),
-                        ("trisweep_exhaustive_4096", lambda: trisweep(qs, ms_, ts, "strict"))]
-                ka, kb = (torch.empty(NS, dtype=torch.int32, device="cuda") for _ in range(2))
-                x, y = trisweep(qs, ms_, ts, "fast", ka)[1], trisweep(qs, ms_, ts, "strict", kb)[1]
-                same = all(bool((p.view(torch.int32) == u.view(torch.int32)).all()) for p, u in zip((*x, ka), (*y, kb)))
-                for _, fn in arms:  # the untimed round
-                    fn()
-                start = float((kind == 15).float().mean())
-                ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
-                for _ in range(a.runs):
-                    for k, fn in arms:
-                        last[k], _, cnt[k] = fn()
-                        ms[k].append(last[k]["kernel_ms"])
-                med = {k: statistics.median(ms[k]) for k, _ in arms}
-                for k, _ in arms:
-                    info = last[k]
-                    tested = info["tris_tested"] if k == "sweep_r0" else info["pairs_tested"]
-                    queries = info["spheres"] if k == "sweep_r0" else info["triangles"]
-                    line = {"scene": name, "set": f"hit_points_{pct}pct_{what}", "arm": k, "queries": cnt[k],
-                            "size": round(size, 6), "found_share": round(info["found"] / max(queries, 1), 4),
-                            "kind15_share": round(start, 4), "mqueries_s": round(cnt[k] / med[k] / 1e3, 2),
-                            "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
-                            "kernel_ms_max": round(max(ms[k]), 4),
-                            "ratio_to_sweep_r0": round((med[k] / cnt[k]) / (med["sweep_r0"] / n), 3),
-                            "ratio_to_clearance": round((med[k] / cnt[k]) / (med["clearance"] / n), 3),
-                            "per_query_ratio_to_exhaustive": round((med[k] / cnt[k]) /
-                                                                   (med["trisweep_exhaustive_4096"] / NS), 6),
-                            "runs": a.runs, "sample_equals_exhaustive": same if k == "trisweep" else None,
-                            "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
-                            "tests_per_query": round(tested / cnt[k], 2),
-                            "gated_per_query": round(info.get("pairs_gated", 0) / cnt[k], 2),
-                            "info": {x: u for x, u in info.items() if x != "kernel_ms"}, "lib_md5": md5}
-                    print(json.dumps(line), flush=True)
-                    if out:
-                        out.write(json.dumps(line) + "\n")
-                        out.flush()
+            arms = [("trisweep", lambda: trisweep(kd=kind)), ("sweep_r0", sphere), ("clearance", clearance),
+                    ("trisweep_exhaustive_4096", lambda: trisweep(qs, ms_, ts, "strict"))]
+            ka, kb = (torch.empty(NS, dtype=torch.int32, device="cuda") for _ in range(2))
+            x, y = trisweep(qs, ms_, ts, "fast", ka)[1], trisweep(qs, ms_, ts, "strict", kb)[1]
+            same = all(bool((p.view(torch.int32) == u.view(torch.int32)).all()) for p, u in zip((*x, ka), (*y, kb)))
+            for _, fn in arms:  # the untimed round
+                fn()
+            start = float((kind == 15).float().mean())
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], _, cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                tested = info["tris_tested"] if k == "sweep_r0" else info["pairs_tested"]
+                queries = info["spheres"] if k == "sweep_r0" else info["triangles"]
+                line = {"scene": name, "set": f"hit_points_{pct}pct_{what}", "arm": k, "queries": cnt[k],
+                        "size": round(size, 6), "found_share": round(info["found"] / max(queries, 1), 4),
+                        "kind15_share": round(start, 4), "mqueries_s": round(cnt[k] / med[k] / 1e3, 2),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_sweep_r0": round((med[k] / cnt[k]) / (med["sweep_r0"] / n), 3),
+                        "ratio_to_clearance": round((med[k] / cnt[k]) / (med["clearance"] / n), 3),
+                        "per_query_ratio_to_exhaustive": round((med[k] / cnt[k]) /
+                                                               (med["trisweep_exhaustive_4096"] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same if k == "trisweep" else None,
+                        "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
+                        "tests_per_query": round(tested / cnt[k], 2),
+                        "gated_per_query": round(info.get("pairs_gated", 0) / cnt[k], 2),
+                        "info": {x: u for x, u in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
+        r.close()
+    if out:
+        out.close()
+
+
+def tricontacts_mode(a, md5):
+    """--mode tricontacts: per scene, on trisweep_mode's six query sets (moving_triangle_sets),
+    rt_sweep_tri_contacts with k = 1, 4, 8 and 16 (tri, t, point and kind written) beside rt_sweep_triangles on the same
+    queries, the swept-volume count (k = 0, count_all, t_max = 1 on every set), and the exhaustive kernel with k = 8 on
+    4,096 of the queries. One untimed round first; then --runs rounds with the arms interleaved; kernel_ms from the HIP
+    events around each launch. One JSON line per arm: median / min / max ms, the ratio of the medians to the sweep's,
+    the per-query ratio to the exhaustive kernel, nodes_visited, pairs_tested and pairs_gated per query, stored and
+    counted per query, the share of starts in contact, the counters, and whether the fast kernel equals the exhaustive
+    one on the 4,096 queries (k = 8 with count_all, and the swept-volume count: every output's bits)."""
+    import torch
+    from prt import device, host
+    W, H, n = a.width, a.height, a.width * a.height
+    NS = 4096
+    out = open(a.out, "a") if a.out else None
+    for name in a.scenes:
+        s = host.Scene.named(name).build_bvh(3)
+        r = device.Renderer(0)
+        r.upload(s)
+        for pct, what, size, ctr, q, mv, tm, (qs, ms_, ts) in moving_triangle_sets(r, s, W, H, NS):
+            one = torch.ones(n, dtype=torch.float32, device="cuda")
+            kind = torch.empty(n, dtype=torch.int32, device="cuda")
+            kinds = {k: torch.empty((n, k), dtype=torch.int32, device="cuda") for k in (1, 4, 8, 16)}
+            torch.cuda.synchronize()
+
+            def sweep():
+                r.sweep_tris(q, mv, t_max=tm, kind=kind)
+                return r.trisweep_info(), n
+
+            def lists(k):
+                r.sweep_tri_contacts(q, mv, k=k, t_max=tm, points_out=True, kind=kinds[k])
+                return r.tricontacts_info(), n
+
+            def volume():
+                r.sweep_tri_contacts(q, mv, k=0, t_max=one, count_all=True)
+                return r.tricontacts_info(), n
+
+            def exhaustive():
+                r.sweep_tri_contacts(qs, ms_, k=8, t_max=ts, points_out=True, kernel="strict")
+                return r.tricontacts_info(), NS
+
+            def sample(k, **kw):
+                x = [r.sweep_tri_contacts(qs, ms_, k=k, points_out=k > 0, kernel=kern, **kw)
+                     for kern in ("fast", "strict")]
+                r.sync()
+                return all(bool((p.view(torch.int32) == u.view(torch.int32)).all()) for p, u in zip(*x))
+
+            same = sample(8, t_max=ts, count_all=True) and sample(0, t_max=one[:NS].contiguous(), count_all=True)
+            arms = [("trisweep", sweep)] + [(f"tricontacts_k{k}", lambda k=k: lists(k)) for k in (1, 4, 8, 16)] + \
+                   [("swept_volume_count", volume), ("tricontacts_k8_exhaustive_4096", exhaustive)]
+            for _, fn in arms:  # the untimed round
+                fn()
+            start = float((kind == 15).float().mean())
+            ms, last, cnt = {k: [] for k, _ in arms}, {}, {}
+            for _ in range(a.runs):
+                for k, fn in arms:
+                    last[k], cnt[k] = fn()
+                    ms[k].append(last[k]["kernel_ms"])
+            med = {k: statistics.median(ms[k]) for k, _ in arms}
+            for k, _ in arms:
+                info = last[k]
+                line = {"scene": name, "set": f"hit_points_{pct}pct_{what}", "arm": k, "queries": cnt[k],
+                        "size": round(size, 6), "found_share": round(info["found"] / max(info["triangles"], 1), 4),
+                        "kind15_share": round(start, 4), "mqueries_s": round(cnt[k] / med[k] / 1e3, 2),
+                        "kernel_ms_median": round(med[k], 4), "kernel_ms_min": round(min(ms[k]), 4),
+                        "kernel_ms_max": round(max(ms[k]), 4),
+                        "ratio_to_trisweep": round((med[k] / cnt[k]) / (med["trisweep"] / n), 3),
+                        "per_query_ratio_to_exhaustive": round((med[k] / cnt[k]) /
+                                                               (med["tricontacts_k8_exhaustive_4096"] / NS), 6),
+                        "runs": a.runs, "sample_equals_exhaustive": same if k == "tricontacts_k8" else None,
+                        "nodes_visited_per_query": round(info["nodes_visited"] / cnt[k], 2),
+                        "tests_per_query": round(info["pairs_tested"] / cnt[k], 2),
+                        "gated_per_query": round(info["pairs_gated"] / cnt[k], 2),
+                        "stored_per_query": round(info.get("stored", 0) / cnt[k], 3),
+                        "counted_per_query": round(info.get("counted", 0) / cnt[k], 3),
+                        "info": {x: u for x, u in info.items() if x != "kernel_ms"}, "lib_md5": md5}
+                print(json.dumps(line), flush=True)
+                if out:
+                    out.write(json.dumps(line) + "\n")
+                    out.flush()
         r.close()
     if out:
         out.close()
