@@ -262,12 +262,17 @@ __device__ __forceinline__ int closest_g(const DScene& s, v3 o, v3 d, float& bes
     bool tie = false;
     best = FMAX;
     nd = 0;
-    if (!degenerate(d) || degenerate_ok(s, o, d)) {  // (as closest)
+    const bool deg = degenerate(d);
+    if (!deg || degenerate_ok(s, o, d)) {  // (as closest)
         const DWide& W = wide_for(s, unit);
         closest_wide_g<G, COUNT>(W, o, d, best, hp, nd, tie, stk, c, q);
-        if (!tie) return hp >= 0 ? W.tri_orig[hp] : -1;
+        if (!tie) {
+            const int orig = hp >= 0 ? W.tri_orig[hp] : -1;
+            // (a degenerate ray's winner: its reference path checked, as closest does)
+            if (!deg || orig < 0 || s.ref_path == nullptr || ref_reaches(s, orig, o, d)) return orig;
+        }
         CTR_INC(c, fb, C_FALLBACK);  // strict re-walk, redundantly in every lane of the group
-        if (TIE_BOUNDED) {  // (bounded just past the tie: closest)
+        if (TIE_BOUNDED && tie) {  // (bounded just past the tie: closest)
             const float tb = tie_bound(o, best), cut = best - (tb - best);
             hp = -1;
             nd = 0;

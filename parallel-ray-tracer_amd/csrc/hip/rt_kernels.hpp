@@ -138,10 +138,13 @@ __device__ __forceinline__ bool degenerate_ok(const DScene& s, v3 o, v3 d) {
     return o.x == o.x && o.y == o.y && o.z == o.z;
 }
 
-// The reference walk reaches triangle t (original index) of a degenerate ray (a zero component of d): no child box
-// on its reference path, leaf to root, has a face at the origin's coordinate along a zero axis -- those the
-// reference's slab test culls (0 / 0, §2). Every box on the path holds the hit point, so it is on no other side of the
-// origin there. The fast walk's winner t, reached, is then the reference's (nothing is hit before it).
+// The reference walk reaches triangle t (original index) of a degenerate ray (a zero component of d): every child box
+// on its reference path, leaf to root, holds the origin's coordinate along a zero axis strictly inside. With the
+// coordinate on a face the reference's slab test divides 0 by 0 (§2), and with it outside by any amount -- (lo - o) / 0
+// and (hi - o) / 0 are then the same infinity -- it culls the box exactly, where hit_triangle's u and v still accept a
+// triangle the ray passes within their rounding of (a ray in the plane x = 0 and an edge at x = -1e-16: the fast walk's
+// padded boxes reach that triangle, the reference never tests it). The fast walk's winner t, reached, is then the
+// reference's (nothing is hit before it); not reached, the ray is walked strictly.
 __device__ __forceinline__ bool ref_reaches(const DScene& s, int t, v3 o, v3 d) {
     const int leaf = s.ref_path[t];
     int cur = ~leaf, r = s.ref_path[s.n_tris + leaf];
@@ -152,9 +155,9 @@ __device__ __forceinline__ bool ref_reaches(const DScene& s, int t, v3 o, v3 d) 
         const bool left = __float_as_int(q.x) == cur;
         const v3 lo = left ? mk(a.x, a.y, a.z) : mk(b.z, b.w, e.x);
         const v3 hi = left ? mk(a.w, b.x, b.y) : mk(e.y, e.z, e.w);
-        if (d.x == 0.0f && (lo.x == o.x || hi.x == o.x)) return false;
-        if (d.y == 0.0f && (lo.y == o.y || hi.y == o.y)) return false;
-        if (d.z == 0.0f && (lo.z == o.z || hi.z == o.z)) return false;
+        if (d.x == 0.0f && !(lo.x < o.x && o.x < hi.x)) return false;
+        if (d.y == 0.0f && !(lo.y < o.y && o.y < hi.y)) return false;
+        if (d.z == 0.0f && !(lo.z < o.z && o.z < hi.z)) return false;
         cur = r;
         r = __float_as_int(q.z);
     }
@@ -1353,9 +1356,11 @@ __device__ __forceinline__ int closest(const DScene& s, v3 o, v3 d, float& best,
     bool tie = false;
     best = FMAX;
     nd = 0;
-    // a degenerate ray whose origin lies on a face: the fast walk, then its winner's reference path checked (chk)
-    const bool face = degenerate(d) && !degenerate_ok(s, o, d);
-    const bool chk = face && s.ref_path != nullptr && o.x == o.x && o.y == o.y && o.z == o.z;
+    // a degenerate ray: the fast walk, then its winner's reference path checked (chk, ref_reaches); without the paths
+    // one whose origin lies on a face walks strictly
+    const bool deg = degenerate(d);
+    const bool face = deg && !degenerate_ok(s, o, d);
+    const bool chk = deg && s.ref_path != nullptr && o.x == o.x && o.y == o.y && o.z == o.z;
     if (!STRICT && (!face || chk)) {
         bool done = false;  // the fast walk's answer stands
         int orig = -1;

@@ -101,8 +101,9 @@ __device__ __forceinline__ int closest_q(const DScene& s, v3 o, v3 d, float o_ma
     nd = 0;
     best = FMAX;
     const bool dom = query_domain(o, d, o_max);
-    const bool face = degenerate(d) && !degenerate_ok(s, o, d);
-    const bool chk = face && s.ref_path != nullptr;
+    const bool deg = degenerate(d);
+    const bool face = deg && !degenerate_ok(s, o, d);
+    const bool chk = deg && s.ref_path != nullptr;  // (every degenerate ray's winner is checked: closest())
     const bool fast = dom && (!face || chk);
     if (s.wide.nodes) {
         const int view = ray_view(s, d);
